@@ -23,6 +23,9 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task description)
                       only on ALL N rows in 65 536-row chunks (--cpu-fit: two sample sizes, fixed + per-row
                       cost fitted and evaluated at N), and value + autograd gradient fitted from two samples (its graph does
                       not fit the host at N = 1M) next to leapfrog_per_s
+
+--dump-outputs DIR writes what the last timed evaluation and the last timed value + gradient returned as DIR/<name>.npy (float64);
+the inputs are seeded (synth), so two builds run with the same arguments can be compared output for output.
 """
 import csv
 import glob
@@ -143,6 +146,20 @@ def cpu_baseline(X, y, Z, sample_rows, full):
                                    "%.2f s, fitted and evaluated at N = %d -> %.1f s" % (g1, tg1, g2, tg2, N, gfull)}}
 
 
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what a caller of the two timed paths received from their last timed call, one float64 .npy per array (about a
+    kilobyte in all).  cb.value -> F, logmarg, trace_term; cb.value_and_grad -> leapfrog_F, leapfrog_logmarg, leapfrog_trace_term
+    and the gradient wrt the natural parameters: grad_ls [d], grad_sf2, grad_s2.  Scalars are stored as shape (1,)."""
+    import numpy as np
+    g = last["g"]
+    arrays = {"F": last["F"], "logmarg": last["parts"]["logmarg"], "trace_term": last["parts"]["trace_term"],
+              "leapfrog_F": last["Fg"], "leapfrog_logmarg": g["logmarg"], "leapfrog_trace_term": g["trace_term"],
+              "grad_ls": g["ls"].detach().cpu().numpy(), "grad_sf2": g["sf2"], "grad_s2": g["s2"]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.atleast_1d(np.asarray(a, dtype=np.float64)))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment): run the N ranks as fresh child processes
     under torch.distributed.run -- one rank per GPU, RCCL over xGMI -- relay their output (rank 0 prints the JSON
@@ -186,7 +203,12 @@ def main():
     ap.add_argument("--side-chain", choices=["on", "off", "graph", "launches"], default="on",
                     help="chol(Kuu) on a side stream beside pass 1 (A/B knob; default = the product default; 'graph' / 'launches' are "
                          "round-4 spellings of 'on': the chain is six plain launches now)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed evaluation and the last timed value + gradient returned "
+                         "as DIR/<name>.npy (float64), so that two builds can be compared output for output on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     LS, SN = float(args.ls), float(args.sig_n)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -252,7 +274,7 @@ def main():
     last = {}
 
     def step_value():
-        last["F"], _ = cb.value(Zd, ls, sf2, s2)
+        last["F"], last["parts"] = cb.value(Zd, ls, sf2, s2)
 
     def step_grad():
         last["Fg"], last["g"] = cb.value_and_grad(Zd, ls, sf2, s2, want_gz=False)
@@ -262,6 +284,8 @@ def main():
     dt_grad = timed(step_grad, max(2, args.steps // 2), 1)
     evals_per_s = args.steps / dt_val
     leap_per_s = max(2, args.steps // 2) / dt_grad
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # dominant kernels, timed alone: the library records HIP events on the launch stream right around them
     # (include/sgp.h: sgp_timing_*; slot 0 kernel assembly, 1 pass-1 contraction, 2 pass-2 contraction)

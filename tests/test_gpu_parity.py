@@ -1013,6 +1013,29 @@ def test_two_ranks_share_the_gpu_real_engine_matches_one_rank():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs on the device: --steps timed evaluations, ms_per_step their mean, and the dumped F the one the result
+    line reports (the last timed evaluation's); the gradient files are finite and of the workload's dimension."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--rows", "131072",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    assert abs(res["ms_per_step"] - 1e3 / res["value"]) < 1e-9 * res["ms_per_step"]
+    F = np.load(str(out / "F.npy"))
+    assert F.dtype == np.float64 and F.shape == (1,) and F[0] == res["F"]
+    g = np.load(str(out / "grad_ls.npy"))
+    assert g.shape == (res["config"]["d"],) and np.isfinite(g).all()
+    assert sum(os.path.getsize(str(out / f)) for f in os.listdir(out)) < 64 << 20
+
+
+@pytest.mark.gpu
 def test_pass1_head_tail_blocks_and_side_stream_assembly(engine):
     """The A/B knob sgp_set_asm_overlap (pass 1 as head block + tail block, the tail's kernel assembly on the library's side stream
     beside the head's contraction): mode 1 (overlapped) and mode 2 (the same blocks enqueued serially) must agree bit for bit, and

@@ -310,6 +310,32 @@ def test_bench_gpus_n_refuses_to_run_n_ranks_on_fewer_devices():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_dump_outputs_writes_what_the_timed_paths_return(tmp_path):
+    """bench.py --dump-outputs DIR: the returns of the two timed calls (cb.value, cb.value_and_grad) as float64 .npy files, bit for
+    bit; and --steps must name a real number of timed steps (0 would leave ms_per_step undefined)."""
+    import importlib.util
+    import subprocess
+    spec = importlib.util.spec_from_file_location("_bench_t", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    G = load_golden("rbf_d3_small")
+    cb = ggp_amd.CollapsedBound(T(G["X"]), T(G["y"]), jitter=float(G["jitter"]), engine=OracleEngine())
+    Z, th = T(G["Z"]), (G["ls"], float(G["sf2"]), float(G["s2"]))
+    last = {}
+    last["F"], last["parts"] = cb.value(Z, *th)
+    last["Fg"], last["g"] = cb.value_and_grad(Z, *th, want_gz=False)
+    bench.dump_outputs(str(tmp_path / "out"), last)
+    got = {os.path.splitext(f)[0]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == sorted(["F", "logmarg", "trace_term", "leapfrog_F", "leapfrog_logmarg", "leapfrog_trace_term",
+                                  "grad_ls", "grad_sf2", "grad_s2"])
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["F"][0] == last["F"] and got["leapfrog_F"][0] == last["Fg"] and got["trace_term"][0] == last["parts"]["trace_term"]
+    assert np.array_equal(got["grad_ls"], last["g"]["ls"].numpy()) and got["grad_s2"][0] == last["g"]["s2"]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr and "{" not in r.stdout
+
+
 def test_device_sampler_run_length_guard():
     """The persistent sampler's sync counters are cumulative ints: a run whose worst case could pass 2^31 is not sent to it
     (HmcTarget.device_sampler_ok(n) answers False and the host-driven sampler takes over; sample_nuts_device itself raises)."""

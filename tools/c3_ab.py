@@ -1,5 +1,5 @@
 import sys, os, math, time, json, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ggp_amd
 eng = ggp_amd.HipEngine()
 if os.environ.get("CU_BUDGET"):

@@ -1,6 +1,6 @@
 import json, math, os, sys, time
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ggp_amd
 eng = ggp_amd.HipEngine()
 for name, N, d, M in (("C3 elevators", 13279, 18, 512), ("C3 reference M", 13279, 18, 100), ("8-GPU shard of C5", 125000, 8, 1024)):
