@@ -78,6 +78,7 @@ PROTOTYPES = {
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_ctx_mixture_predict": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _dp, _dp, _dp, _dbl, _i32, _i32, _i32, _i32,
                                        _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_ctx_mixture_predict_zs": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dp, _dp, _dbl, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_timing_enable": (None, [_i32]),
     "sgp_timing_last_ms": (_i32, [_i32, C.POINTER(C.c_float)]),
     "sgp_timing_last_rows": (_i64, [_i32]),
@@ -160,6 +161,9 @@ PROTOTYPES = {
     "sgp_small_nuts_stat_cols": (_sz, []),
     "sgp_small_nuts": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _dbl, _i32, _i32, _i32, _dbl, _dbl,
                               C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_small_nuts_joint_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_small_nuts_joint": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _i32, _i32, _i32, _dbl, _dbl, C.c_uint64,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_suffstats_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "sgp_suffstats_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _dbl, _vp, _vp, _dbl, _vp, _i64, _i32, _i32, _i32,
                                  _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -180,6 +184,7 @@ PROTOTYPES = {
     "sgp_mixture_predict_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
     "sgp_mixture_predict": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _dp, _dp, _dp, _dbl, _i32, _i32, _i32, _i32, _dbl,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_mixture_predict_zs": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dp, _dp, _dbl, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_svgp_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _vp, _i32, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_gauss_hermite": (_i32, [_i32, _dp, _dp]),

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
+
 import torch
 
 try:  # torch.distributed is plumbing; single-process use never touches it
@@ -885,3 +887,82 @@ class HmcTarget:
         grad.append(sf * (2.0 * sf * g["sf2"] + pg_sf) + 1.0)
         grad.append(sn * (2.0 * sn * g["s2"] + pg_sn) + 1.0)
         return F + lp + sum(float(v) for v in theta), grad
+
+
+# ---------------------------------------------------------------------------------------------
+# joint HMC target: theta AND the inducing inputs  (reference models/all_in_HMC.py:45-61)
+# ---------------------------------------------------------------------------------------------
+_HALF_LOG_2PI = 0.9189385332046727
+
+
+class JointHmcTarget:
+    """logp(q) and its gradient for NUTS over the hyper-parameters and the inducing inputs together,
+    q = [log ls_1..d, log sig_f, log sig_n, vec(Z)] with Z row-major M x d, untransformed (ndim = d + 2 + M d).
+
+    The same VFE ``MarginalSparse`` density and theta priors / Jacobians as ``HmcTarget``, plus Z ~ Normal(0, 1)
+    elementwise with its normalising constants, so ``logp`` is PyMC3's model logp.  Kuu jitter 1e-6 (``stabilize``).
+    A value of theta outside the representable range or a failed factorisation gives -inf, never an exception."""
+
+    def __init__(self, bound: CollapsedBound, M: int):
+        if bound.kernel == "composite":
+            raise ValueError("the joint target takes stationary kernels (no dF/dZ for composite kernels)")
+        self.bound = bound
+        self.d = bound.d
+        self.M = int(M)
+        self.ndim = self.d + 2 + self.M * self.d
+
+    def start(self):
+        """PyMC3's test point: HmcTarget's for theta, the prior mean 0 for Z."""
+        return [math.log(2.0)] * self.d + [0.0, 0.0] + [0.0] * (self.M * self.d)
+
+    def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
+        """True when ``hmc.sample_nuts_device`` can run this target (``sgp_small_nuts_joint``): the single-launch class with dF/dZ,
+        one rank, and -- when the run length is given -- a worst case inside the persistent kernel's counters."""
+        b = self.bound
+        ok = hasattr(b.engine, "small_nuts_joint") and b._small_ok(self.M, want_gz=True)
+        return ok and (n_draws_total is None or device_run_fits(int(b.X.shape[0]), n_draws_total, max_treedepth))
+
+    def _split(self, q):
+        q = q.tolist() if hasattr(q, "tolist") else [float(v) for v in q]
+        return q[:self.d + 2], q[self.d + 2:]
+
+    def constrain(self, q):
+        th, z = self._split(q)
+        return {"ls": [math.exp(v) for v in th[:self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1]),
+                "Z": np.asarray(z, dtype=np.float64).reshape(self.M, self.d)}
+
+    def logp(self, q):
+        return self.logp_and_grad(q)[0]
+
+    def logp_and_grad(self, q):
+        """Returns (logp, grad list[ndim]).  One call = one leapfrog's evaluation, dF/dZ included."""
+        th, z = self._split(q)
+        bad = (-math.inf, [0.0] * self.ndim)
+        if not HmcTarget._in_range(th) or not all(math.isfinite(v) for v in z):
+            return bad
+        b = self.bound
+        zz = np.asarray(z, dtype=np.float64)
+        Zt = torch.from_numpy(zz.reshape(self.M, self.d)).to(b.engine.device)
+        zprior = -0.5 * float(zz @ zz) - _HALF_LOG_2PI * zz.size
+        if b._small_ok(self.M, want_gz=True):
+            # ONE launch: priors and Jacobians of theta on the device (mode SGP_SMALL_HMC), dF/dZ beside them
+            h, info, gz = b._small_eval(Zt, th, 1, True, True)
+            b.n_evals += 1
+            b.n_grads += 1
+            hl = h.tolist()
+            if info != 0 or not math.isfinite(hl[0]):
+                return bad
+            gzl = (gz.detach().to("cpu").numpy().reshape(-1) - zz).tolist()
+            return hl[0] + zprior, hl[1:self.d + 3] + gzl
+        p = self.constrain(q)
+        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+        F, g = b.value_and_grad(Zt, ls, sf * sf, sn * sn, want_gz=True, raise_on_fail=False)
+        if g.get("info", 0) != 0 or not math.isfinite(F):
+            return bad
+        lp, pg_ls, pg_sf, pg_sn = HmcTarget._prior(ls, sf, sn)
+        gl = g["ls"].tolist()
+        grad = [ls[j] * (gl[j] + pg_ls[j]) + 1.0 for j in range(self.d)]
+        grad.append(sf * (2.0 * sf * g["sf2"] + pg_sf) + 1.0)
+        grad.append(sn * (2.0 * sn * g["s2"] + pg_sn) + 1.0)
+        gz = g["Z"].detach().to("cpu").numpy().reshape(-1) - zz
+        return F + lp + sum(th) + zprior, grad + gz.tolist()

@@ -263,3 +263,13 @@ extern "C" int sgp_ctx_bound_from_whitened_stats(sgp_ctx* ctx, const double* W, 
   return sgp_bound_from_whitened_stats_ex(W, u, yy, kappa, s2, N, M, with_adjoints, out, Phibar, bbar, Kuubar, factors, kuu_linv, info,
                                           Cw, ws, ws_bytes, stream);
 }
+extern "C" int sgp_ctx_mixture_predict_zs(sgp_ctx* ctx, const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs,
+                                          int64_t ldxs, int64_t T, const double* Z, int64_t ldz, int64_t z_stride, int S,
+                                          const double* inv_ls, const double* sf2, const double* s2, double jitter, int M, int d,
+                                          int kernel_id, int pred_noise, double gate_jitter, double* mean, double* var, double* cov,
+                                          int* info, int* gate_info, void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  CtxScope scope(ctx);
+  return sgp_mixture_predict_zs(X, ldx, y, N, Xs, ldxs, T, Z, ldz, z_stride, S, inv_ls, sf2, s2, jitter, M, d, kernel_id, pred_noise,
+                                gate_jitter, mean, var, cov, info, gate_info, ws, ws_bytes, stream);
+}

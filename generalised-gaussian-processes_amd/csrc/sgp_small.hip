@@ -27,6 +27,7 @@
 // All cross-workgroup sums go through partial arrays reduced in a fixed order: results are bit-reproducible.
 #include "sgp_potrf.hpp"
 #include "sgp_nuts.hpp"
+#include "sgp_nuts_wide.hpp"
 #include "sgp_composite.hpp"
 
 namespace sgp {
@@ -1704,6 +1705,132 @@ __global__ __launch_bounds__(256) void small_nuts_kernel(SmallArgs a, NutsArgs n
   }
 }
 
+// ---- device-resident joint NUTS (all_in_HMC: theta AND the inducing inputs) ------------------------------------------
+// The persistent launch of small_nuts_kernel with a WIDE position q = [log ls (d), log sig_f, log sig_n, vec(Z) (M d)]: the 256
+// threads of workgroup 0 run sgp_nuts_wide.hpp between the evaluations, every vector in device memory (JointArgs::wide).  The
+// evaluation is sm_eval_body in mode SGP_SMALL_HMC with want_gz = 1 and a.Z pointing INTO the published position (ldz = d).
+// Workgroup 0 adds the Z ~ Normal(0, 1) prior (value: one fixed-order reduction; gradient: dF/dZ - Z).
+struct JointArgs {
+  const double* q0;   // start, ndim doubles
+  double* pos;        // the published position (= a.theta; a.Z = pos + d + 2)
+  double* grad;       // ndim: the gradient the sampler reads
+  double* wide;       // wide_ws_doubles(ndim)
+  double* samples;    // n_draws x ndim
+  double* stats;      // n_draws x SGP_NUTS_STAT_COLS
+  long long* counters;  // [0] evaluations, [1] draws finished, [2] / [3] s_memrealtime ticks in the sampler / the evaluations
+  int ndim, n_tune, n_draws, max_treedepth;
+  double step_scale, target_accept;
+  unsigned long long seed;
+};
+
+template <int MP>
+__global__ __launch_bounds__(256) void small_nuts_joint_kernel(SmallArgs a, JointArgs ja) {
+  __shared__ SmKernelShared<MP> ks;
+  __shared__ WideState st;
+  __shared__ int cmd;
+  __shared__ double lp_sh;
+  const int tid = threadIdx.x, wg = blockIdx.x, ndim = ja.ndim, nth = a.d + 2, nz = a.M * a.d;
+  int* sy = a.sync;
+  int* abortw = sy + SY_ABORT * SM_SYNC_STRIDE;
+  if (tid == 0) ks.dead = 0;
+  int ev = 0, req = 0;
+  unsigned long long t_draw = 0, t_mark = 0, t_samp = 0, t_eval = 0;
+  const WideWs w = wide_ws_carve(ja.wide, ndim);
+  const SmallArgs al = a;
+  if (wg == 0) {
+    wnuts_init(st, w, tid, ndim, ja.n_tune, ja.n_draws, ja.max_treedepth, ja.step_scale, ja.target_accept, ja.seed, ja.q0);
+    if (tid == 0) {
+      lp_sh = 0.0;
+      t_draw = t_mark = __builtin_amdgcn_s_memrealtime();
+    }
+  }
+  __syncthreads();
+  for (;;) {
+    ++req;
+    if (wg == 0) {
+      // HAZARD (early overwrite of Z): the next position may only be written once no workgroup reads the current one any more.
+      // The evaluation reads Z from the published position while it runs (staged Z rows, the Kuu adjoint's slabs), so the
+      // other workgroups acknowledge a request only AFTER their evaluation has returned (below), not after reading theta as
+      // in small_nuts_kernel; thread 0 waits for all acknowledgements of the previous request before any thread of this
+      // workgroup writes the position inside wnuts_step.
+      if (tid == 0 && !sm_wait_ack(sy + SY_ACK * SM_SYNC_STRIDE, (req - 1) * ((int)gridDim.x - 1), abortw)) ks.dead = 1;
+      __syncthreads();
+      const int it0 = st.it;
+      const int c = ks.dead ? NUTS_DONE : wnuts_step(st, w, tid, lp_sh, ja.grad, ja.pos, ja.samples, ja.stats);
+      if (tid == 0) {
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        if (st.it != it0) {
+          const int row = it0 - ja.n_tune;
+          if (row >= 0) ja.stats[(size_t)ja.n_draws * NST_COLS + row] = (double)(now - t_draw) * 1e-8;
+          t_draw = now;
+        }
+        t_samp += now - t_mark;
+        t_mark = now;
+        cmd = c;
+      }
+      __syncthreads();
+      if (cmd != NUTS_EVAL) {
+        if (tid == 0) {
+          if (ks.dead) *a.info = SGP_INFO_TIMEOUT;  // an acknowledgement never came: the run did not finish
+          ja.counters[0] = st.n_leapfrog;
+          ja.counters[1] = st.it;
+          ja.counters[2] = (long long)t_samp;
+          ja.counters[3] = (long long)t_eval;
+        }
+        sm_publish_set(sy + SY_DONE * SM_SYNC_STRIDE, 1);
+        sm_publish_set(sy + SY_REQ * SM_SYNC_STRIDE, req);  // (its release fence also covers the position written above)
+        break;
+      }
+      sm_publish_set(sy + SY_REQ * SM_SYNC_STRIDE, req);
+      __syncthreads();
+    } else {
+      if (!sm_wait_ge(sy + SY_REQ * SM_SYNC_STRIDE, req, abortw, &ks.dead)) break;
+      if (sm_ld(sy + SY_DONE * SM_SYNC_STRIDE) != 0) break;
+    }
+    sm_hypers<false>(a, ks.hyp);  // every workgroup from the same theta: the same decision everywhere
+    bool evaluated = false;
+    if (!ks.dead && ks.hyp.ok) {
+      ++ev;
+      sm_eval_call<MP, false>(&al, &ks, ev);
+      evaluated = true;
+    }
+    // the last read of this request's Z is behind us: acknowledge (see the hazard above)
+    if (wg != 0 && tid == 0) __hip_atomic_fetch_add(sy + SY_ACK * SM_SYNC_STRIDE, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    if (ks.dead || (evaluated && sm_ld(abortw) != 0)) {
+      if (wg == 0 && tid == 0) *a.info = SGP_INFO_TIMEOUT;
+      break;
+    }
+    if (wg != 0) continue;
+    __syncthreads();
+    // HAZARD (incomplete dF/dZ): with more than SM_GZ_SPREAD gradient partials the final dF/dZ reduction runs in the row
+    // workgroups; sm_eval_body's chain workgroup waits for their SY_GZ count (acquire) before it writes a.out, so once the
+    // evaluation has returned here every entry of a.gZ is final and visible to this workgroup.
+    const bool ok = evaluated && *a.info == 0 && isfinite(a.out[0]);
+    double zz[1] = {0.0};
+    if (ok) {
+      WN_NO_CONTRACT  // the Z prior rounds like the sampler's own sums
+      const double* zp = ja.pos + nth;
+      WN_FOR(i, ndim) ja.grad[i] = i < nth ? a.out[1 + i] : a.gZ[i - nth] - zp[i - nth];
+      wn_reduce<1>(st, tid, nz, [&](int i, double* v) { v[0] += zp[i] * zp[i]; }, zz);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      // a failed factorisation or theta out of range is a divergence, not an error
+      lp_sh = ok ? a.out[0] + (-0.5 * zz[0] - 0.9189385332046727 * (double)nz) : -INFINITY;
+      if (!evaluated) *a.info = 0;
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+      t_eval += now - t_mark;
+      t_mark = now;
+    }
+    __syncthreads();
+  }
+  if (wg == 0) {
+    __syncthreads();
+    for (int e = tid; e < SY_WORDS * SM_SYNC_STRIDE; e += 256)
+      if (e / SM_SYNC_STRIDE != SY_REQ && e / SM_SYNC_STRIDE != SY_DONE) sy[e] = 0;
+  }
+}
+
 struct SmallWs {
   SmallArgs a;
   size_t bytes;
@@ -1989,5 +2116,60 @@ extern "C" int sgp_small_eval_batch(const double* X, int64_t ldx, const double* 
   zero_ints(a.sync + SY_REQ * SM_SYNC_STRIDE, 2 * SM_SYNC_STRIDE, st);
   if (M <= 64) small_nuts_kernel<64, false><<<grid, 256, 0, st>>>(a, na);
   else small_nuts_kernel<128, false><<<grid, 256, 0, st>>>(a, na);
+  return check_launch();
+}
+
+// ---- device-resident joint NUTS: workspace = the single-launch workspace | the position | the gradient | dF/dZ | the wide
+// sampler's vectors
+static size_t small_joint_extra_doubles(int M, int d) {
+  const int nd = d + 2 + M * d;
+  return 2 * (size_t)nd + (size_t)M * d + wide_ws_doubles(nd);
+}
+extern "C" size_t sgp_small_nuts_joint_workspace_bytes(int64_t N, int M, int d) {
+  if (!sgp_small_supported(N, M, d, SGP_KERNEL_RBF)) return 0;
+  const size_t base = (sgp_small_workspace_bytes(N, M, d) + 255) / 256 * 256;
+  return base + small_joint_extra_doubles(M, d) * sizeof(double);
+}
+
+extern "C" int sgp_small_nuts_joint(const double* X, int64_t ldx, const double* y, const double* q0, int64_t N, int M, int d,
+                                    int kernel_id, double jitter, int n_tune, int n_draws, int max_treedepth, double step_scale,
+                                    double target_accept, uint64_t seed, double* samples, double* stats, long long* counters,
+                                    double* out, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!X || !y || !q0 || !samples || !stats || !counters || !out || !info || ldx < d) return SGP_ERR_ARG;
+  if (kernel_id == SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;  // no dF/dZ for composite kernels
+  if (n_tune < 0 || n_draws < 1 || max_treedepth < 1 || max_treedepth >= NUTS_MAXDEPTH || !(step_scale > 0.0)) return SGP_ERR_ARG;
+  if (!sgp_small_supported(N, M, d, kernel_id)) return SGP_ERR_DIM;
+  SmallWs w = carve_small(ws, N, M, d);
+  const size_t base = (w.bytes + 255) / 256 * 256;
+  if (!ws || ws_bytes < base + small_joint_extra_doubles(M, d) * sizeof(double)) return SGP_ERR_WORKSPACE;
+  SmallArgs& a = w.a;
+  if (int rc = small_kernel_fields(a, d, kernel_id, SGP_SMALL_HMC, nullptr)) return rc;
+  // HAZARD (counter overflow): the sync counters are cumulative ints (evaluations x contributing workgroups); a run whose worst
+  // case -- every tree at its depth limit -- could pass 2^31 is refused up front, as in sgp_small_nuts
+  const double worst = ((double)n_tune + (double)n_draws + 2.0) * (double)(1 << max_treedepth) * (double)small_grid(M, a.grow);
+  if (worst > 2.0e9) return SGP_ERR_DIM;
+  const int nd = d + 2 + M * d;
+  double* extra = reinterpret_cast<double*>(static_cast<char*>(ws) + base);
+  JointArgs ja{};
+  ja.q0 = q0;
+  ja.pos = extra;
+  ja.grad = extra + nd;
+  double* gz = extra + 2 * (size_t)nd;
+  ja.wide = gz + (size_t)M * d;
+  ja.samples = samples; ja.stats = stats; ja.counters = counters;
+  ja.ndim = nd; ja.n_tune = n_tune; ja.n_draws = n_draws; ja.max_treedepth = max_treedepth;
+  ja.step_scale = step_scale; ja.target_accept = target_accept; ja.seed = seed;
+  a.X = X; a.ldx = ldx; a.y = y; a.theta = ja.pos; a.Z = ja.pos + d + 2; a.ldz = d;
+  a.N = (int)N; a.M = M; a.d = d; a.kid = kernel_id; a.mode = SGP_SMALL_HMC; a.want_grad = 1; a.want_gz = 1;
+  a.jitter = jitter;
+  a.info = info; a.out = out; a.gZ = gz;
+  a.stamps = nullptr;
+  const int grid = small_grid(M, a.grow);
+  hipStream_t st = (hipStream_t)stream;
+  if (!(M <= 64 ? small_grid_is_resident<small_nuts_joint_kernel<64>>(grid) : small_grid_is_resident<small_nuts_joint_kernel<128>>(grid)))
+    return SGP_ERR_LAUNCH;
+  zero_ints(a.sync + SY_REQ * SM_SYNC_STRIDE, 2 * SM_SYNC_STRIDE, st);
+  if (M <= 64) small_nuts_joint_kernel<64><<<grid, 256, 0, st>>>(a, ja);
+  else small_nuts_joint_kernel<128><<<grid, 256, 0, st>>>(a, ja);
   return check_launch();
 }

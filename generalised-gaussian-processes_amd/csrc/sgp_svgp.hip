@@ -432,9 +432,11 @@ __global__ __launch_bounds__(256) void svgp_prep_batch_kernel(const double* __re
 
 // Kp[s] = Kuu(theta_s) + jitter I, padded with the identity (the factorization's input), Mp x Mp
 template <int KID>
-__global__ __launch_bounds__(256) void svgp_kuu_batch_kernel(const double* __restrict__ Z, int64_t ldz, SvgpThetaS th, double jitter, int M,
-                                                             int Mp, double* __restrict__ Kp) {
+// z_stride: doubles between the inducing inputs of consecutive samples (0: one Z for all of them)
+__global__ __launch_bounds__(256) void svgp_kuu_batch_kernel(const double* __restrict__ Z, int64_t ldz, int64_t z_stride, SvgpThetaS th,
+                                                             double jitter, int M, int Mp, double* __restrict__ Kp) {
   const KernArgs& ka = th.ka[blockIdx.y];
+  Z += (int64_t)blockIdx.y * z_stride;
   double* K = Kp + (int64_t)blockIdx.y * Mp * Mp;
   const int64_t total = (int64_t)Mp * Mp;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -454,10 +456,11 @@ __global__ __launch_bounds__(256) void svgp_kuu_batch_kernel(const double* __res
 }
 
 template <int KID>
-__global__ __launch_bounds__(256) void svgp_kub_batch_kernel(const double* __restrict__ Z, int64_t ldz, const double* __restrict__ Xb,
-                                                             int64_t ldx, SvgpThetaS th, int M, int Mp, int B, int Bp,
-                                                             double* __restrict__ Kub) {
+__global__ __launch_bounds__(256) void svgp_kub_batch_kernel(const double* __restrict__ Z, int64_t ldz, int64_t z_stride,
+                                                             const double* __restrict__ Xb, int64_t ldx, SvgpThetaS th, int M, int Mp,
+                                                             int B, int Bp, double* __restrict__ Kub) {
   const KernArgs& ka = th.ka[blockIdx.y];
+  Z += (int64_t)blockIdx.y * z_stride;
   const int64_t total = (int64_t)Mp * Bp;
   double* K = Kub + (int64_t)blockIdx.y * total;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -1041,16 +1044,16 @@ static int svgp_batch_impl(int phase, const double* Xb, int64_t ldx, const doubl
     svgp_prep_batch_kernel<<<gmm, 256, 0, st>>>(LS, m, M, Mp, w.LSp, w.mp, info, S);
     svgp_kl_kernel<<<64, 256, 0, st>>>(m, LS, M, w.kl);
     switch (kernel_id) {
-      case SGP_KERNEL_RBF: svgp_kuu_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
-      case SGP_KERNEL_MATERN32: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
-      default: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
+      case SGP_KERNEL_RBF: svgp_kuu_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, 0, th, jitter, M, Mp, w.Kp); break;
+      case SGP_KERNEL_MATERN32: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, 0, th, jitter, M, Mp, w.Kp); break;
+      default: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, 0, th, jitter, M, Mp, w.Kp); break;
     }
     potrf_lower_batch(w.Kp, w.Linv, Mp, Mp, S, mm, info, w.flags, st);
     tri_inverse(w.Kp, w.Linv, w.tmp, Mp, Mp, st, S, mm);
     switch (kernel_id) {
-      case SGP_KERNEL_RBF: svgp_kub_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
-      case SGP_KERNEL_MATERN32: svgp_kub_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
-      default: svgp_kub_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
+      case SGP_KERNEL_RBF: svgp_kub_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, 0, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
+      case SGP_KERNEL_MATERN32: svgp_kub_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, 0, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
+      default: svgp_kub_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmb, S), 256, 0, st>>>(Z, ldz, 0, Xb, ldx, th, M, Mp, (int)B, Bp, w.Kub); break;
     }
     GemmDesc a;  // A = L^-1 Kub
     a.A = w.Linv; a.lda = Mp; a.B = w.Kub; a.ldb = Bp; a.C = w.A; a.ldc = Bp;
@@ -1185,11 +1188,13 @@ extern "C" size_t sgp_mixture_predict_workspace_bytes(int64_t N, int64_t T, int 
   return carve_mix(nullptr, padded_m(M), Cc, Tp, S, want_cov != 0, want_gate != 0).bytes;
 }
 
-extern "C" int sgp_mixture_predict(const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs, int64_t ldxs, int64_t T,
-                                   const double* Z, int64_t ldz, int S, const double* inv_ls, const double* sf2, const double* s2,
-                                   double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter, double* mean,
-                                   double* var, double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes,
-                                   sgp_stream_t stream) {
+// sample s uses the inducing inputs Z + s z_stride (z_stride 0: one Z for all samples, sgp_mixture_predict)
+static int mixture_predict_impl(const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs, int64_t ldxs, int64_t T,
+                                const double* Z, int64_t ldz, int64_t z_stride, int S, const double* inv_ls, const double* sf2,
+                                const double* s2, double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter,
+                                double* mean, double* var, double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes,
+                                sgp_stream_t stream) {
+  if (z_stride < 0 || (z_stride > 0 && z_stride < (int64_t)(M - 1) * ldz + d)) return SGP_ERR_ARG;  // samples' Z must not overlap
   if (!X || !y || !Xs || !Z || !inv_ls || !sf2 || !s2 || !mean || !info || N < 1 || T < 1 || M <= 0 || d <= 0 || ldx < d || ldxs < d || ldz < d)
     return SGP_ERR_ARG;
   if (S < 1 || S > SVGP_MAX_S || kernel_id < 0 || kernel_id > SGP_KERNEL_MATERN52) return SGP_ERR_ARG;
@@ -1217,18 +1222,18 @@ extern "C" int sgp_mixture_predict(const double* X, int64_t ldx, const double* y
   auto kmat = [&](const double* P, int64_t ldp, int n, int np, double* out) {  // K(Z, P) for every sample: Mp x np, zero padded
     const dim3 grid(grid_for_s((int64_t)Mp * np), S);
     switch (kernel_id) {
-      case SGP_KERNEL_RBF: svgp_kub_batch_kernel<SGP_KERNEL_RBF><<<grid, 256, 0, st>>>(Z, ldz, P, ldp, th, M, Mp, n, np, out); break;
-      case SGP_KERNEL_MATERN32: svgp_kub_batch_kernel<SGP_KERNEL_MATERN32><<<grid, 256, 0, st>>>(Z, ldz, P, ldp, th, M, Mp, n, np, out); break;
-      default: svgp_kub_batch_kernel<SGP_KERNEL_MATERN52><<<grid, 256, 0, st>>>(Z, ldz, P, ldp, th, M, Mp, n, np, out); break;
+      case SGP_KERNEL_RBF: svgp_kub_batch_kernel<SGP_KERNEL_RBF><<<grid, 256, 0, st>>>(Z, ldz, z_stride, P, ldp, th, M, Mp, n, np, out); break;
+      case SGP_KERNEL_MATERN32: svgp_kub_batch_kernel<SGP_KERNEL_MATERN32><<<grid, 256, 0, st>>>(Z, ldz, z_stride, P, ldp, th, M, Mp, n, np, out); break;
+      default: svgp_kub_batch_kernel<SGP_KERNEL_MATERN52><<<grid, 256, 0, st>>>(Z, ldz, z_stride, P, ldp, th, M, Mp, n, np, out); break;
     }
   };
 
   // ---- train side: L, L^-1, W = A A^T, u = A y over row chunks, B, L_B^-1, q -------------------------------------------
   zero_ints(info, S, st);
   switch (kernel_id) {
-    case SGP_KERNEL_RBF: svgp_kuu_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
-    case SGP_KERNEL_MATERN32: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
-    default: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, th, jitter, M, Mp, w.Kp); break;
+    case SGP_KERNEL_RBF: svgp_kuu_batch_kernel<SGP_KERNEL_RBF><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, z_stride, th, jitter, M, Mp, w.Kp); break;
+    case SGP_KERNEL_MATERN32: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN32><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, z_stride, th, jitter, M, Mp, w.Kp); break;
+    default: svgp_kuu_batch_kernel<SGP_KERNEL_MATERN52><<<dim3(gmm, S), 256, 0, st>>>(Z, ldz, z_stride, th, jitter, M, Mp, w.Kp); break;
   }
   potrf_lower_batch(w.Kp, w.Linv, Mp, Mp, S, mm, info, w.flags, st);
   tri_inverse(w.Kp, w.Linv, w.tmp, Mp, Mp, st, S, mm);
@@ -1314,4 +1319,22 @@ extern "C" int sgp_svgp_predict(const double* Xs, int64_t ldxs, int64_t T, const
   crop_copy(w.mu, 1, mean, 1, (int)T, 1, st);
   crop_copy(w.v, 1, var, 1, (int)T, 1, st);
   return check_launch();
+}
+
+extern "C" int sgp_mixture_predict(const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs, int64_t ldxs, int64_t T,
+                                   const double* Z, int64_t ldz, int S, const double* inv_ls, const double* sf2, const double* s2,
+                                   double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter, double* mean,
+                                   double* var, double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes,
+                                   sgp_stream_t stream) {
+  return mixture_predict_impl(X, ldx, y, N, Xs, ldxs, T, Z, ldz, 0, S, inv_ls, sf2, s2, jitter, M, d, kernel_id, pred_noise, gate_jitter,
+                              mean, var, cov, info, gate_info, ws, ws_bytes, stream);
+}
+
+extern "C" int sgp_mixture_predict_zs(const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs, int64_t ldxs, int64_t T,
+                                      const double* Z, int64_t ldz, int64_t z_stride, int S, const double* inv_ls, const double* sf2,
+                                      const double* s2, double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter,
+                                      double* mean, double* var, double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes,
+                                      sgp_stream_t stream) {
+  return mixture_predict_impl(X, ldx, y, N, Xs, ldxs, T, Z, ldz, z_stride, S, inv_ls, sf2, s2, jitter, M, d, kernel_id, pred_noise,
+                              gate_jitter, mean, var, cov, info, gate_info, ws, ws_bytes, stream);
 }

@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -476,10 +477,12 @@ class HipEngine:
     def small_supported(self, N: int, M: int, d: int, kernel="rbf") -> bool:
         return bool(self._cf.sgp_small_supported(int(N), int(M), int(d), _kernel_id(kernel)))
 
-    def _small_ws(self, N, M, d):
-        nbytes = self.lib.sgp_small_workspace_bytes(N, M, d)
-        if nbytes == 0:
+    def _small_ws(self, N, M, d, nbytes=None):
+        """nbytes: at least this many (sgp_small_nuts_joint's workspace extends the single-launch one)."""
+        base = self.lib.sgp_small_workspace_bytes(N, M, d)
+        if base == 0:
             raise ValueError("shape N=%d M=%d d=%d is outside the single-launch path" % (N, M, d))
+        nbytes = max(int(nbytes or 0), int(base))
         # one workspace per HIP stream: the launch's sync words live in it, so two evaluations in flight on different streams
         # of one engine must not share them (ADVICE r2)
         key = ("small", int(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else 0)
@@ -606,6 +609,45 @@ class HipEngine:
         c = counters.to("cpu")
         res = {"samples": samples.to("cpu"), "stats": h[: n_draws * (cols - 1)].reshape(n_draws, cols - 1),
                "seconds": h[n_draws * (cols - 1):], "evaluations": int(c[0]), "draws": int(c[1]), "info": int(info.to("cpu")[0])}
+        if res["info"] < 0:
+            self.small_reset()
+        return res
+
+    def small_nuts_joint(self, X, y, M, q0, n_tune, n_draws, seed, jitter=1e-6, kernel="rbf", max_treedepth=10, step_scale=0.25,
+                         target_accept=0.8):
+        """Joint NUTS over theta and the M x d inducing inputs in one persistent launch (sgp_small_nuts_joint); q0 = [log ls,
+        log sig_f, log sig_n, vec(Z)].  Returns the dict of ``small_nuts`` (samples [n_draws, d + 2 + M d]) plus the device
+        seconds workgroup 0 spent in the sampler and in the evaluations (``sampler_seconds``, ``eval_seconds``)."""
+        N, d = X.shape
+        M = int(M)
+        for t, n in ((X, "X"), (y, "y")):
+            self._chk(t, n)
+        if _kernel_id(kernel) == _kernel_id("composite"):
+            raise ValueError("the joint sampler takes stationary kernels")
+        nd = d + 2 + M * d
+        q0d = torch.as_tensor(np.asarray(q0, dtype=np.float64).reshape(-1)).to(self.device)
+        if q0d.numel() != nd:
+            raise ValueError("q0 has %d entries, expected %d" % (q0d.numel(), nd))
+        nbytes = self.lib.sgp_small_nuts_joint_workspace_bytes(N, M, d)
+        if nbytes == 0:
+            raise ValueError("shape N=%d M=%d d=%d is outside the single-launch path" % (N, M, d))
+        small = self._small_ws(N, M, d, nbytes)  # the per-stream single-launch workspace, sized to hold the sampler's vectors too
+        cols = int(self.lib.sgp_small_nuts_stat_cols())
+        samples = self.empty(n_draws, nd)
+        stats = torch.zeros(n_draws * cols, dtype=torch.float64, device=self.device)
+        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        out = self.empty(d + 5)
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check("sgp_small_nuts_joint", self._cf.sgp_small_nuts_joint(
+            self._ptr(X), d, self._ptr(y), self._ptr(q0d), N, M, d, _kernel_id(kernel), float(jitter), int(n_tune), int(n_draws),
+            int(max_treedepth), float(step_scale), float(target_accept), int(seed) & ((1 << 64) - 1), self._ptr(samples),
+            self._ptr(stats), C.c_void_p(counters.data_ptr()), self._ptr(out), C.c_void_p(info.data_ptr()), self._ptr(small),
+            small.numel(), self._stream()))
+        h = stats.to("cpu")
+        c = counters.to("cpu")
+        res = {"samples": samples.to("cpu"), "stats": h[: n_draws * (cols - 1)].reshape(n_draws, cols - 1),
+               "seconds": h[n_draws * (cols - 1):], "evaluations": int(c[0]), "draws": int(c[1]), "info": int(info.to("cpu")[0]),
+               "sampler_seconds": int(c[2]) * 1e-8, "eval_seconds": int(c[3]) * 1e-8}
         if res["info"] < 0:
             self.small_reset()
         return res
@@ -835,17 +877,21 @@ class HipEngine:
     MIXTURE_BATCH = 8  # hyper-parameter samples per sgp_mixture_predict call
 
     def mixture_predict(self, X, y, Xs, Z, ls, sf2, s2, jitter=1e-6, kernel="rbf", pred_noise=True, full_cov=False, gate_jitter=None):
-        """Predictive of the collapsed bound at S hyper-parameter samples (ls: S x d, sf2, s2: S host sequences), eight samples
+        """Predictive of the collapsed bound at S hyper-parameter samples (ls: S x d, sf2, s2: S host sequences; Z: M x d, or S x M x d
+        for inducing inputs of their own per sample -- all_in_HMC's draws, sgp_mixture_predict_zs), eight samples
         per chain of launches.  Returns dict(mean [S, T], var [S, T], cov [S, T, T] or None, info [S] int32, gate [S] int32 or
         None: status of cholesky(cov + gate_jitter I), the reference's PSD gate) -- device tensors, nothing synchronised."""
         import ctypes
         N, d = X.shape
         T = Xs.shape[0]
-        M = Z.shape[0]
+        per_z = Z.dim() == 3  # (S, M, d): inducing inputs of their own for every sample (sgp_mixture_predict_zs)
+        M = Z.shape[-2]
         for t, n in ((X, "X"), (y, "y"), (Xs, "Xs"), (Z, "Z")):
             self._chk(t, n)
         lsv = [[float(v) for v in row] for row in ls]
         S = len(lsv)
+        if per_z and (Z.shape[0] != S or Z.shape[2] != d):
+            raise ValueError("a per-sample Z must be S x M x d")
         if any(len(row) != d for row in lsv) or len(sf2) != S or len(s2) != S:
             raise ValueError("ls must be S x d, sf2 and s2 of length S")
         want_gate = full_cov and gate_jitter is not None
@@ -862,12 +908,14 @@ class HipEngine:
             inv = (ctypes.c_double * (n * d))(*[1.0 / v for row in lsv[s0:s0 + n] for v in row])
             sf2c = (ctypes.c_double * n)(*[float(v) for v in sf2[s0:s0 + n]])
             s2c = (ctypes.c_double * n)(*[float(v) for v in s2[s0:s0 + n]])
-            st = self.lib.sgp_ctx_mixture_predict(
-                self._c(), self._ptr(X), d, self._ptr(y), N, self._ptr(Xs), d, T, self._ptr(Z), d, n, inv, sf2c, s2c, float(jitter), M, d,
+            zargs = (C.c_void_p(Z.data_ptr() + 8 * s0 * M * d), d, M * d) if per_z else (self._ptr(Z), d)
+            fn = self.lib.sgp_ctx_mixture_predict_zs if per_z else self.lib.sgp_ctx_mixture_predict
+            st = fn(
+                self._c(), self._ptr(X), d, self._ptr(y), N, self._ptr(Xs), d, T, *zargs, n, inv, sf2c, s2c, float(jitter), M, d,
                 _kernel_id(kernel), 1 if pred_noise else 0, float(gate_jitter) if want_gate else 0.0, self._ptr(mean[s0:]), self._ptr(var[s0:]),
                 self._ptr(cov[s0:]) if full_cov else None, C.c_void_p(info[s0:].data_ptr()),
                 C.c_void_p(gate[s0:].data_ptr()) if want_gate else None, self._ptr(ws), ws.numel(), self._stream())
-            _lib.check("sgp_mixture_predict", st)
+            _lib.check("sgp_mixture_predict_zs" if per_z else "sgp_mixture_predict", st)
         return {"mean": mean, "var": var, "cov": cov, "info": info, "gate": gate}
 
     def svgp_predict(self, Xs, Z, ls, sf2, m, LS, jitter=1e-6, kernel="rbf"):

@@ -345,11 +345,19 @@ def shared_seed(seed: Optional[int], group=None) -> Optional[int]:
     return int(t.item())
 
 
+def _trace_row(c, q):
+    """One trace row: the constrained hyper-parameters, the unconstrained position, and Z (M x d) when the target samples it."""
+    row = {"ls": np.asarray(c["ls"], dtype=np.float64), "sig_f": float(c["sig_f"]), "sig_n": float(c["sig_n"]), "theta_unc": q.copy()}
+    if "Z" in c:
+        row["Z"] = np.asarray(c["Z"], dtype=np.float64)
+    return row
+
+
 def sample_nuts_device(target, n_samples: int, tune: int, seed: Optional[int] = None, start: Optional[Sequence[float]] = None,
                        step_scale=0.25, target_accept=0.8, max_treedepth=10) -> Trace:
     """``pm.sample(n_samples, tune=tune, chains=1)`` entirely on the GPU: one persistent launch (``sgp_small_nuts``) runs the
     sampler and every leapfrog's evaluation; theta, the momentum and the sampler state never visit the host (SURVEY section 8
-    f-1).  ``target`` is an ``HmcTarget`` or ``CompositeHmcTarget`` whose bound takes the single-launch path (M <= 128, one rank).  Same algorithm and
+    f-1).  ``target`` is an ``HmcTarget``, ``CompositeHmcTarget`` or ``JointHmcTarget`` (``sgp_small_nuts_joint``) whose bound takes the single-launch path (M <= 128, one rank).  Same algorithm and
     random stream as ``NUTS(..., rng=SplitMix(seed))``; the trace has the surface the reference reads
     (``trace['ls']``, ``trace[i]``, ``get_sampler_stats('step_size' | 'perf_counter_diff')``)."""
     b = target.bound
@@ -376,9 +384,14 @@ def sample_nuts_device(target, n_samples: int, tune: int, seed: Optional[int] = 
         raise RuntimeError("could not find a starting point with finite log-density" if start is None
                            else "the log-density is not finite at the supplied start")
     t0 = time.perf_counter()
-    extra = target.device_sampler_args() if hasattr(target, "device_sampler_args") else {}  # composite kernels: the structure
-    r = b.engine.small_nuts(b.X, b.y, target.Z, q, tune, n_samples, rng.s, jitter=b.jitter, kernel=b.kernel,
-                            max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept, **extra)
+    from .core import JointHmcTarget
+    if isinstance(target, JointHmcTarget):  # Z is part of the position
+        r = b.engine.small_nuts_joint(b.X, b.y, target.M, q, tune, n_samples, rng.s, jitter=b.jitter, kernel=b.kernel,
+                                      max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept)
+    else:
+        extra = target.device_sampler_args() if hasattr(target, "device_sampler_args") else {}  # composite kernels: the structure
+        r = b.engine.small_nuts(b.X, b.y, target.Z, q, tune, n_samples, rng.s, jitter=b.jitter, kernel=b.kernel,
+                                max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept, **extra)
     wall = time.perf_counter() - t0
     if r["info"] < 0:
         from .core import SgpTimeoutError
@@ -390,9 +403,7 @@ def sample_nuts_device(target, n_samples: int, tune: int, seed: Optional[int] = 
     th = r["samples"].numpy()
     samples = []
     for row in th:
-        c = target.constrain(row)
-        samples.append({"ls": np.asarray(c["ls"], dtype=np.float64), "sig_f": float(c["sig_f"]), "sig_n": float(c["sig_n"]),
-                        "theta_unc": row.copy()})
+        samples.append(_trace_row(target.constrain(row), row))
     st = r["stats"].numpy()
     stats = {"step_size": st[:, 0], "tree_size": st[:, 1], "depth": st[:, 2], "mean_tree_accept": st[:, 3],
              "diverging": st[:, 4] != 0.0, "energy": st[:, 5], "logp": st[:, 6], "perf_counter_diff": r["seconds"].numpy()}
@@ -445,9 +456,7 @@ def sample_nuts(target, n_samples: int, tune: int, seed: Optional[int] = None, s
         if progress is not None:
             progress(it, st)
         if not tuning:
-            c = target.constrain(q)
-            samples.append({"ls": np.asarray(c["ls"], dtype=np.float64), "sig_f": float(c["sig_f"]), "sig_n": float(c["sig_n"]),
-                            "theta_unc": q.copy()})
+            samples.append(_trace_row(target.constrain(q), q))
             stat_rows.append(st)
     keys = ("step_size", "tree_size", "depth", "mean_tree_accept", "diverging", "energy", "perf_counter_diff", "logp")
     stats = {k: np.array([r[k] for r in stat_rows]) for k in keys}

@@ -4,6 +4,8 @@ Mirrors (same names, argument meaning, return shapes and error behaviour):
   * ``SparseGPR``                      reference models/sgpr.py:22-160
   * ``BayesianSparseGPR_HMC``          reference models/bayesian_sgpr_hmc.py:26-196
   * ``mixture_posterior_predictive``   reference models/bayesian_sgpr_hmc.py:198-231
+  * ``all_in_HMC``                     reference models/all_in_HMC.py:24-82
+  * ``full_mixture_posterior_predictive``  reference models/all_in_HMC.py:84-119
 
 Differences that are deliberate and documented: the device is taken from the inputs
 at construction (R16); ``model.inducing_points`` always tracks the optimised Z (R8); ``train_model``
@@ -17,7 +19,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .core import CollapsedBound, HmcTarget, NotPositiveDefiniteError, SgpTimeoutError, few_host_threads
+from .core import CollapsedBound, HmcTarget, JointHmcTarget, NotPositiveDefiniteError, SgpTimeoutError, few_host_threads
 from .gp_shim import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, LazyPredictive,
                       MultivariateNormal, RBFKernel, ScaleKernel, TrainPrior, ZeroMean)
 from .hmc import Trace, sample_nuts, sample_nuts_device
@@ -320,6 +322,129 @@ def mixture_posterior_predictive(model, test_x, trace_hyper):
                 preds.append(pred)
             except SgpTimeoutError:
                 raise  # a device scheduling fault is never a numerical outcome: it must not thin the mixture silently
+            except (RuntimeError, NotPositiveDefiniteError):
+                print('Not psd for sample ' + str(i))
+    return preds
+
+
+# ---------------------------------------------------------------------------------------------
+# all_in_HMC: NUTS over theta AND the inducing inputs
+# ---------------------------------------------------------------------------------------------
+class all_in_HMC(SparseGPR):  # noqa: N801  (reference class name)
+    """Fully Bayesian sparse GP: NUTS over (ls, sig_f, sig_n) and Z ~ Normal(0, 1) of shape (M, d) jointly, on the VFE
+    ``MarginalSparse`` density (reference models/all_in_HMC.py:24-82).  M is ``Z_init``'s row count (the reference always
+    samples 100 rows); ``Z_init`` only binds the model's inducing inputs until a trace rebinds them."""
+
+    def __init__(self, train_x, train_y, likelihood, Z_init, engine=None, seed: Optional[int] = None):
+        super().__init__(train_x, train_y, likelihood, Z_init, engine=engine, jitter=0.0)
+        self.data_dim = self.train_x.shape[1]
+        self._seed = seed
+        self._n_hmc_calls = 0
+        self._hmc_cb: Optional[CollapsedBound] = None
+        self.device_sampler = True  # the persistent joint kernel when the problem takes the single-launch path (M <= 128)
+
+    def _hmc_bound(self):
+        if self._hmc_cb is None:  # PyMC3 stabilises Kuu with 1e-6 I
+            self._hmc_cb = CollapsedBound(self.train_x, self.train_y, kernel="rbf", jitter=1e-6, engine=self._bound().engine)
+        return self._hmc_cb
+
+    def sample(self, n_samples, input_dim, tune) -> Trace:
+        """``pm.sample(n_samples, tune=tune, chains=1)`` over the joint model; ``trace['Z']`` has shape (n, M, d)."""
+        if int(input_dim) != self.data_dim:
+            raise ValueError("input_dim %d does not match the training inputs (%d)" % (input_dim, self.data_dim))
+        target = JointHmcTarget(self._hmc_bound(), self.num_inducing)
+        seed = None if self._seed is None else self._seed + self._n_hmc_calls
+        self._n_hmc_calls += 1
+        if self.device_sampler and target.device_sampler_ok(n_samples + tune):
+            return sample_nuts_device(target, n_samples, tune, seed=seed)
+        return sample_nuts(target, n_samples, tune, seed=seed)
+
+    def train_model(self):
+        """500 tuning + 100 draws (reference models/all_in_HMC.py:63-79).  Returns (trace_hyper, [step_size], [perf_time sum])."""
+        self.train()
+        self.likelihood.train()
+        trace_hyper = self.sample(100, self.data_dim, 500)
+        return (trace_hyper, [trace_hyper.get_sampler_stats('step_size')[0]],
+                [trace_hyper.get_sampler_stats('perf_counter_diff').sum()])
+
+    def optimal_q_u(self):
+        return self(self.covar_module.inducing_points)
+
+
+def _bind_sample(model, hyper_sample):
+    model.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
+    model.base_covar_module.outputscale = hyper_sample['sig_f'] ** 2
+    model.base_covar_module.base_kernel.lengthscale = hyper_sample['ls']
+    with torch.no_grad():
+        Zp = model.covar_module.inducing_points
+        Zp.data = torch.as_tensor(np.asarray(hyper_sample['Z']), dtype=torch.float64).to(Zp.device).reshape(Zp.shape).clone()
+
+
+def _full_mixture_batched(model, test_x, trace_hyper):
+    """full_mixture_posterior_predictive's predictives from sgp_mixture_predict_zs, or None where it does not apply."""
+    b = model._bound()
+    e = b.engine
+    if not hasattr(e, "mixture_predict") or b.world != 1 or b.kernel == "composite" or len(trace_hyper) == 0:
+        return None
+    tx = test_x[:, None] if test_x.dim() == 1 else test_x
+    if tx.shape[0] > FULL_COV_MAX_T or tx.shape[0] > 8192:
+        return None
+    S, d = len(trace_hyper), b.d
+    ls = [np.asarray(trace_hyper[i]['ls'], dtype=np.float64).reshape(-1) for i in range(S)]
+    ls = [np.repeat(v, d) if v.size == 1 and d > 1 else v for v in ls]
+    sf2 = [float(trace_hyper[i]['sig_f']) ** 2 for i in range(S)]
+    s2 = [float(trace_hyper[i]['sig_n']) ** 2 for i in range(S)]
+    Zs = np.stack([np.asarray(trace_hyper[i]['Z'], dtype=np.float64).reshape(-1, d) for i in range(S)])
+    Xs = tx.detach().to(dtype=torch.float64, device=e.device).contiguous()
+    with torch.no_grad():
+        r = e.mixture_predict(b.X, b.y, Xs, torch.from_numpy(Zs).to(e.device), ls, sf2, s2, jitter=b.jitter, kernel=b.kernel,
+                              pred_noise=True, full_cov=True, gate_jitter=1e-5)
+        status = torch.stack([r["info"], r["gate"]]).to("cpu")
+    model.train()
+    model.likelihood.train()
+    _bind_sample(model, trace_hyper[S - 1])
+    model.eval()
+    model.likelihood.eval()
+    preds = []
+    for i in range(S):
+        info, gate = int(status[0, i]), int(status[1, i])
+        if info < 0 or gate < 0:
+            raise SgpTimeoutError()
+        if info != 0 or gate != 0:
+            print('Not psd for sample ' + str(i))
+            continue
+        preds.append(MultivariateNormal(r["mean"][i], r["cov"][i], variance=r["var"][i], engine=e))
+    return preds
+
+
+def full_mixture_posterior_predictive(model, test_x, trace_hyper):
+    """One predictive per joint draw, each with THAT draw's Z (reference models/all_in_HMC.py:84-119): a draw with
+    sig_n^2 < 1e-4 gets sig_n = 0.01 (as in the reference, the trace row itself is changed); a predictive whose covariance fails
+    cholesky(cov + 1e-5 I) is skipped with "Not psd for sample i".  The model is left at the last draw, Z included.
+    Batched through sgp_mixture_predict_zs (eight draws per chain of launches, each with its own Z); the per-draw loop below is
+    the fallback where that does not apply (test double, several ranks, T beyond the full-covariance limit)."""
+    for i in range(len(trace_hyper)):
+        if trace_hyper[i]['sig_n'] ** 2 < 1e-4:
+            trace_hyper[i]['sig_n'] = 0.01
+    batched = _full_mixture_batched(model, test_x, trace_hyper)
+    if batched is not None:
+        return batched
+    preds = []
+    for i in range(len(trace_hyper)):
+        hyper_sample = trace_hyper[i]
+        model.train()
+        model.likelihood.train()
+        _bind_sample(model, hyper_sample)
+        with torch.no_grad():
+            model.eval()
+            model.likelihood.eval()
+            try:
+                pred = model.likelihood(model(test_x))
+                if not pred.is_psd(1e-5):
+                    raise RuntimeError("predictive covariance not positive definite")
+                preds.append(pred)
+            except SgpTimeoutError:
+                raise
             except (RuntimeError, NotPositiveDefiniteError):
                 print('Not psd for sample ' + str(i))
     return preds

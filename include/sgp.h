@@ -193,6 +193,12 @@ int sgp_ctx_mixture_predict(sgp_ctx* ctx, const double* X, int64_t ldx, const do
                             int64_t T, const double* Z, int64_t ldz, int S, const double* inv_ls, const double* sf2, const double* s2,
                             double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter, double* mean, double* var,
                             double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+/* sgp_mixture_predict_zs with the context's device and options */
+int sgp_ctx_mixture_predict_zs(sgp_ctx* ctx, const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs,
+                               int64_t ldxs, int64_t T, const double* Z, int64_t ldz, int64_t z_stride, int S, const double* inv_ls,
+                               const double* sf2, const double* s2, double jitter, int M, int d, int kernel_id, int pred_noise,
+                               double gate_jitter, double* mean, double* var, double* cov, int* info, int* gate_info, void* ws,
+                               size_t ws_bytes, sgp_stream_t stream);
 
 /* ---- deprecated process-wide switches (ABI version 1): each one sets the matching option of the DEFAULT context ---- */
 /* The single-launch dataflow factorization keeps every workgroup resident (one per CU) and sizes its grid from the device's CU
@@ -542,6 +548,21 @@ int sgp_small_nuts(const double* X, int64_t ldx, const double* y, const double* 
                    double* stats, long long* counters, double* out, int* info,
                    void* ws, size_t ws_bytes, sgp_stream_t stream);
 
+/* device-resident JOINT NUTS (all_in_HMC): the sampler of sgp_small_nuts over q = [log ls (d), log sig_f, log sig_n, vec(Z)]
+ * (Z row-major M x d, untransformed, ndim = d + 2 + M d): the NUTS target of sgp_small_eval (mode SGP_SMALL_HMC) with dF/dZ,
+ * plus Z ~ Normal(0, 1) elementwise.  Z is not an input: it is part of q0 and of every draw.
+ *   q0 (device, ndim): the start;  samples (device, n_draws x ndim);  stats as for sgp_small_nuts;
+ *   counters (device, 4 x int64): evaluations, draws finished, s_memrealtime ticks (100 MHz) spent in the sampler and in the
+ *   evaluations by workgroup 0;  out (device, d + 5) and info as for sgp_small_nuts.
+ * Stationary kernels only (SGP_KERNEL_COMPOSITE -> SGP_ERR_ARG); ws of sgp_small_nuts_joint_workspace_bytes(N, M, d) bytes (0:
+ * outside the single-launch class), its first sgp_small_sync_bytes() zeroed once.  Same co-residency rules, max_treedepth <= 11,
+ * and the same refusal (SGP_ERR_DIM) of runs whose worst case could overflow the sync counters.                            */
+size_t sgp_small_nuts_joint_workspace_bytes(int64_t N, int M, int d);
+int sgp_small_nuts_joint(const double* X, int64_t ldx, const double* y, const double* q0, int64_t N, int M, int d,
+                         int kernel_id, double jitter, int n_tune, int n_draws, int max_treedepth, double step_scale,
+                         double target_accept, uint64_t seed, double* samples, double* stats, long long* counters,
+                         double* out, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+
 /* device-resident NUTS over the composite target of sgp_small_eval_composite (mode SGP_SMALL_HMC): q0, theta_scratch and the
  * rows of `samples` have n_free + 1 entries (<= 18), `out` n_free + 4.                                                    */
 int sgp_small_nuts_composite(const double* X, int64_t ldx, const double* y, const double* Z, int64_t ldz,
@@ -679,6 +700,15 @@ int sgp_mixture_predict(const double* X, int64_t ldx, const double* y, int64_t N
                         double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter,
                         double* mean, double* var, double* cov, int* info, int* gate_info,
                         void* ws, size_t ws_bytes, sgp_stream_t stream);
+/* sgp_mixture_predict with inducing inputs of their own for every sample (all_in_HMC's draws): sample s uses the M x d rows at
+ * Z + s z_stride (leading dimension ldz); z_stride 0 is sgp_mixture_predict, bit for bit.  Same workspace query
+ * (sgp_mixture_predict_workspace_bytes), S <= 8, info / gate_info conventions; overlapping samples (0 < z_stride <
+ * (M - 1) ldz + d) -> SGP_ERR_ARG. */
+int sgp_mixture_predict_zs(const double* X, int64_t ldx, const double* y, int64_t N, const double* Xs, int64_t ldxs, int64_t T,
+                           const double* Z, int64_t ldz, int64_t z_stride, int S, const double* inv_ls, const double* sf2,
+                           const double* s2, double jitter, int M, int d, int kernel_id, int pred_noise, double gate_jitter,
+                           double* mean, double* var, double* cov, int* info, int* gate_info, void* ws, size_t ws_bytes,
+                           sgp_stream_t stream);
 /* latent predictive mean / variance of q(f*) at T rows (models/svgp.py:132-141 continues through the likelihood) */
 int sgp_svgp_predict(const double* Xs, int64_t ldxs, int64_t T, const double* Z, int64_t ldz, const double* inv_ls,
                      double sf2, double jitter, const double* m, const double* LS, int M, int d, int kernel_id,
