@@ -188,6 +188,15 @@ PROTOTYPES = {
     "sgp_svgp_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _vp, _i32, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_gauss_hermite": (_i32, [_i32, _dp, _dp]),
+    # the exact GP marginal likelihood and its predictive (GPR_HMC)
+    "sgp_exact_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_exact_factors_len": (_sz, [_i64]),
+    "sgp_exact_eval": (_i32, [_vp, _i64, _vp, _i64, _i32, _dp, _dbl, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_ctx_exact_eval": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _dp, _dbl, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_exact_predict_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "sgp_exact_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_ctx_exact_predict": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                     _sz, _vp]),
     "sgp_predict_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "sgp_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _i32, _i32, _i32, _i32,
                            _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -890,6 +890,87 @@ class HmcTarget:
 
 
 # ---------------------------------------------------------------------------------------------
+# exact-GP HMC target  (reference models/gpr_hmc.py:43-59)
+# ---------------------------------------------------------------------------------------------
+EXACT_MAX_N = 4096  # SGP_MAX_INDUCING: the largest N sgp_exact_eval factors
+
+
+class ExactHmcTarget:
+    """logp(theta_unc) and its gradient for NUTS over the EXACT GP marginal likelihood, theta_unc = [log ls_1..d, log sig_f, log sig_n].
+
+    ``pm.gp.Marginal(cov_func=sig_f**2 * ExpQuad(ls)).marginal_likelihood(y, X, noise=sig_n)`` with ls ~ Gamma(2, 1), sig_f ~
+    HalfCauchy(1), sig_n ~ HalfCauchy(1), log-transformed: the density is log N(y | 0, K + (sig_n^2 + jitter) I) plus
+    ``HmcTarget``'s priors and log-Jacobians.  ``jitter`` defaults to 0: Marginal adds only WhiteNoise(sig_n) to the diagonal.
+    One ``logp_and_grad`` is one ``engine.exact_eval`` (include/sgp.h: sgp_exact_eval) and one device-to-host copy.  A non-zero
+    status word (A numerically not positive definite, the conditioning gate) or a non-finite F gives (-inf, zeros), which the
+    sampler treats as a divergence; it never raises.  Single process: the target makes no collectives (N <= 4096 fits one device)."""
+
+    def __init__(self, X, y, kernel="rbf", engine=None, jitter=0.0):
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine(X.device if X.is_cuda else None)
+        if kernel not in ("rbf", "matern32", "matern52"):
+            raise ValueError("ExactHmcTarget takes 'rbf', 'matern32' or 'matern52' (got %r)" % (kernel,))
+        self.engine = engine
+        if X.dim() == 1:
+            X = X[:, None]
+        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
+        self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
+        if self.X.shape[0] != self.y.shape[0]:
+            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
+        if self.X.shape[0] > EXACT_MAX_N:
+            raise ValueError("the exact GP takes at most N = %d training rows (got %d)" % (EXACT_MAX_N, self.X.shape[0]))
+        self.kernel = kernel
+        self.jitter = float(jitter)
+        self.d = int(self.X.shape[1])
+        self.ndim = self.d + 2
+        self.n_evals = 0
+
+    def start(self):
+        """PyMC3's test point in the unconstrained space (``HmcTarget.start``)."""
+        return [math.log(2.0)] * self.d + [0.0, 0.0]
+
+    def constrain(self, theta):
+        th = [float(v) for v in theta]
+        return {"ls": [math.exp(v) for v in th[: self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1])}
+
+    def _eval(self, theta, want_grad):
+        p = self.constrain(theta)
+        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+        self.n_evals += 1
+        return p, self.engine.exact_eval(self.X, self.y, ls, sf * sf, sn * sn + self.jitter, kernel=self.kernel, want_grad=want_grad)
+
+    def logp(self, theta):
+        theta = theta.tolist() if hasattr(theta, "tolist") else [float(v) for v in theta]
+        if not HmcTarget._in_range(theta):
+            return -math.inf
+        p, r = self._eval(theta, False)
+        if r["info"] != 0 or not math.isfinite(r["F"]):
+            return -math.inf
+        lp = HmcTarget._prior(p["ls"], p["sig_f"], p["sig_n"])[0]
+        return r["F"] + lp + sum(theta)
+
+    def logp_and_grad(self, theta):
+        """Returns (logp, grad list[d+2])."""
+        theta = theta.tolist() if hasattr(theta, "tolist") else [float(v) for v in theta]
+        bad = (-math.inf, [0.0] * self.ndim)
+        if not HmcTarget._in_range(theta):
+            return bad
+        p, r = self._eval(theta, True)
+        if r["info"] != 0 or not math.isfinite(r["F"]):
+            return bad
+        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+        lp, pg_ls, pg_sf, pg_sn = HmcTarget._prior(ls, sf, sn)
+        gl = r["ls"]
+        grad = [ls[j] * (gl[j] + pg_ls[j]) + 1.0 for j in range(self.d)]  # d/d log ls = ls d/d ls ; + Jacobian 1
+        grad.append(sf * (2.0 * sf * r["sf2"] + pg_sf) + 1.0)
+        grad.append(sn * (2.0 * sn * r["s2"] + pg_sn) + 1.0)
+        if not all(math.isfinite(v) for v in grad):
+            return bad
+        return r["F"] + lp + sum(theta), grad
+
+
+# ---------------------------------------------------------------------------------------------
 # joint HMC target: theta AND the inducing inputs  (reference models/all_in_HMC.py:45-61)
 # ---------------------------------------------------------------------------------------------
 _HALF_LOG_2PI = 0.9189385332046727

@@ -273,3 +273,18 @@ extern "C" int sgp_ctx_mixture_predict_zs(sgp_ctx* ctx, const double* X, int64_t
   return sgp_mixture_predict_zs(X, ldx, y, N, Xs, ldxs, T, Z, ldz, z_stride, S, inv_ls, sf2, s2, jitter, M, d, kernel_id, pred_noise,
                                 gate_jitter, mean, var, cov, info, gate_info, ws, ws_bytes, stream);
 }
+extern "C" int sgp_ctx_exact_eval(sgp_ctx* ctx, const double* X, int64_t ldx, const double* y, int64_t N, int d, const double* inv_ls,
+                                  double sf2, double s2, int kernel_id, int with_grad, double* out, double* grads, double* factors, int* info,
+                                  void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  CtxScope scope(ctx);
+  return sgp_exact_eval(X, ldx, y, N, d, inv_ls, sf2, s2, kernel_id, with_grad, out, grads, factors, info, ws, ws_bytes, stream);
+}
+extern "C" int sgp_ctx_exact_predict(sgp_ctx* ctx, const double* Xs, int64_t ldxs, int64_t T, const double* X, int64_t ldx, int64_t N, int d,
+                                     const double* inv_ls, double sf2, double s2, const double* factors, int kernel_id, int pred_noise,
+                                     double* mean, double* var, double* cov, void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  CtxScope scope(ctx);
+  return sgp_exact_predict(Xs, ldxs, T, X, ldx, N, d, inv_ls, sf2, s2, factors, kernel_id, pred_noise, mean, var, cov, ws, ws_bytes,
+                           stream);
+}

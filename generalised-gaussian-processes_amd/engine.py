@@ -737,6 +737,53 @@ class HipEngine:
         _lib.check("sgp_predict", st)
         return mean, var, cov
 
+    # ------------------------------------------------------------------ exact GP marginal likelihood (GPR_HMC)
+    EXACT_HEAD = 6  # doubles ahead of the gradient in an exact_eval result buffer: out (4) | status word | pad
+
+    def exact_eval(self, X, y, ls, sf2, s2, kernel="rbf", want_grad=True, want_factors=False):
+        """log N(y | 0, K(X, X) + s2 I) and, with ``want_grad``, its gradient (include/sgp.h: sgp_exact_eval).  Everything the host
+        reads -- F, y^T A^-1 y, log|A|, tr A^-1, the status word and the d + 2 gradient entries -- lands in ONE result buffer that
+        comes back in one device-to-host copy.  Returns dict(F, out=[4 floats], info, and with ``want_grad`` ls=[d], sf2, s2; with
+        ``want_factors`` factors= the opaque device buffer ``exact_predict`` consumes).  A non-zero ``info`` (A numerically not
+        positive definite, the conditioning gate, a time-out) is reported, never raised."""
+        N, d = X.shape
+        self._chk(X, "X"), self._chk(y, "y")
+        H = self.EXACT_HEAD
+        buf = self.empty(H + d + 2)
+        info = buf[4:5].view(torch.int32)[:1]
+        factors = self.empty(self.lib.sgp_exact_factors_len(N)) if want_factors else None
+        ws = self._workspace("exact", self.lib.sgp_exact_workspace_bytes(N, d, 1 if want_grad else 0))
+        base = buf.data_ptr()
+        st = self.lib.sgp_ctx_exact_eval(
+            self._c(), self._ptr(X), d, self._ptr(y), N, d, self._inv_ls(ls, d, kernel), float(sf2), float(s2), _kernel_id(kernel),
+            1 if want_grad else 0, C.c_void_p(base), C.c_void_p(base + 8 * H) if want_grad else C.c_void_p(0), self._ptr(factors),
+            self._ptr(info), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_exact_eval", st)
+        host = buf.to("cpu")
+        vals = host.tolist()
+        res = {"F": vals[0], "out": vals[:4], "info": int(host[4:5].numpy().view("int32")[0])}
+        if want_grad:
+            res.update(ls=vals[H:H + d], sf2=vals[H + d], s2=vals[H + d + 1])
+        if want_factors:
+            res["factors"] = factors
+        return res
+
+    def exact_predict(self, Xs, X, ls, sf2, s2, factors, kernel="rbf", pred_noise=True, full_cov=False):
+        """Exact posterior predictive at the rows of Xs from ``exact_eval(..., want_factors=True)``'s factors at the same (X, theta)
+        (include/sgp.h: sgp_exact_predict).  Returns (mean, var, cov or None) as device tensors; nothing is synchronised."""
+        T, d = Xs.shape
+        N = X.shape[0]
+        self._chk(Xs, "Xs"), self._chk(X, "X"), self._chk(factors, "factors")
+        mean, var = self.empty(T), self.empty(T)
+        cov = self.empty(T, T) if full_cov else None
+        ws = self._workspace("exact_predict", self.lib.sgp_exact_predict_workspace_bytes(T, N, d, 1 if full_cov else 0))
+        st = self.lib.sgp_ctx_exact_predict(
+            self._c(), self._ptr(Xs), d, T, self._ptr(X), d, N, d, self._inv_ls(ls, d, kernel), float(sf2), float(s2), self._ptr(factors),
+            _kernel_id(kernel), 1 if pred_noise else 0, self._ptr(mean), self._ptr(var), self._ptr(cov), self._ptr(ws), ws.numel(),
+            self._stream())
+        _lib.check("sgp_exact_predict", st)
+        return mean, var, cov
+
     # ------------------------------------------------------------------ SVGP minibatch bound (SURVEY 8 f-3)
     def svgp_elbo(self, Xb, yb, Z, ls, sf2, s2, m, LS, N_total, jitter=1e-6, kernel="rbf", likelihood="gaussian",
                   with_grads=False):

@@ -5,7 +5,8 @@ Mirrors (same names, argument meaning, return shapes and error behaviour):
   * ``BayesianSparseGPR_HMC``          reference models/bayesian_sgpr_hmc.py:26-196
   * ``mixture_posterior_predictive``   reference models/bayesian_sgpr_hmc.py:198-231
   * ``all_in_HMC``                     reference models/all_in_HMC.py:24-82
-  * ``full_mixture_posterior_predictive``  reference models/all_in_HMC.py:84-119
+  * ``full_mixture_posterior_predictive``  reference models/all_in_HMC.py:84-119 (and models/gpr_hmc.py:84-119 for a GPR_HMC)
+  * ``GPR_HMC``                        reference models/gpr_hmc.py:23-81
 
 Differences that are deliberate and documented: the device is taken from the inputs
 at construction (R16); ``model.inducing_points`` always tracks the optimised Z (R8); ``train_model``
@@ -19,7 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .core import CollapsedBound, HmcTarget, JointHmcTarget, NotPositiveDefiniteError, SgpTimeoutError, few_host_threads
+from .core import (EXACT_MAX_N, CollapsedBound, ExactHmcTarget, HmcTarget, JointHmcTarget, NotPositiveDefiniteError, SgpTimeoutError,
+                   few_host_threads)
 from .gp_shim import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, LazyPredictive,
                       MultivariateNormal, RBFKernel, ScaleKernel, TrainPrior, ZeroMean)
 from .hmc import Trace, sample_nuts, sample_nuts_device
@@ -417,12 +419,133 @@ def _full_mixture_batched(model, test_x, trace_hyper):
     return preds
 
 
+# ---------------------------------------------------------------------------------------------
+# GPR_HMC: NUTS over theta on the exact marginal likelihood
+# ---------------------------------------------------------------------------------------------
+class GPR_HMC(ExactGP):  # noqa: N801  (reference class name)
+    """Exact GP regression with (ls, sig_f, sig_n) sampled by NUTS on the exact marginal likelihood (reference models/gpr_hmc.py:23-81):
+    the yardstick that shows what sparsity costs.  Priors as ``BayesianSparseGPR_HMC``; covariance sig_f^2 ExpQuad(ls), noise sig_n,
+    no jitter (``ExactHmcTarget``).  N <= 4096 training rows.  ``model(x)`` follows ExactGP: the prior in training mode, the exact
+    posterior at the bound hyper-parameters in eval mode (full covariance); ``likelihood(model(x))`` adds the noise."""
+
+    def __init__(self, train_x, train_y, likelihood, engine=None, seed: Optional[int] = None):
+        super().__init__(train_x, train_y, likelihood)
+        if train_x.dim() == 1:
+            train_x = train_x[:, None]
+        if train_x.shape[0] > EXACT_MAX_N:
+            raise ValueError("GPR_HMC factors the exact N x N covariance: at most N = %d training rows (got %d)"
+                             % (EXACT_MAX_N, train_x.shape[0]))
+        self.train_x = train_x
+        self.train_y = train_y
+        self.data_dim = self.train_x.shape[1]
+        self.likelihood = likelihood
+        self.mean_module = ZeroMean()
+        self.covar_module = ScaleKernel(RBFKernel(ard_num_dims=self.data_dim))
+        self._engine = engine
+        self._seed = seed
+        self._n_hmc_calls = 0
+        self._target: Optional[ExactHmcTarget] = None
+        dev = engine.device if engine is not None else train_x.device
+        self.to(dev)
+
+    def _exact_target(self) -> ExactHmcTarget:
+        if self._target is None:
+            self._target = ExactHmcTarget(self.train_x, self.train_y, kernel="rbf", engine=self._engine)
+            self._engine = self._target.engine
+        return self._target
+
+    def _hypers(self):
+        ls = self.covar_module.base_kernel.lengthscale.detach().reshape(-1).tolist()
+        return ls, float(self.covar_module.outputscale.detach()), float(self.likelihood.noise.detach())
+
+    def forward(self, x):
+        if x.dim() == 1:
+            x = x[:, None]
+        t = self._exact_target()
+        e = t.engine
+        ls, sf2, s2 = self._hypers()
+        xs = x.detach().to(dtype=torch.float64, device=e.device).contiguous()
+        if self.training:  # the prior N(0, K(x, x))
+            return MultivariateNormal(torch.zeros(xs.shape[0], dtype=torch.float64, device=e.device), e.kuu(xs, ls, sf2, 0.0),
+                                      engine=self._dev_engine())
+        if xs.shape[0] > FULL_COV_MAX_T:
+            return LazyPredictive(self, x)
+        return self._predict(xs, pred_noise=False)
+
+    def _dev_engine(self):
+        e = self._exact_target().engine
+        return e if getattr(e, "device", None) is not None and e.device.type == "cuda" else None
+
+    def _predict(self, test_x, pred_noise=True):
+        if test_x.dim() == 1:
+            test_x = test_x[:, None]
+        t = self._exact_target()
+        e = t.engine
+        ls, sf2, s2 = self._hypers()
+        r = e.exact_eval(t.X, t.y, ls, sf2, s2, kernel=t.kernel, want_grad=False, want_factors=True)
+        if r["info"] < 0:
+            raise SgpTimeoutError()
+        if r["info"] != 0:
+            raise NotPositiveDefiniteError(r["info"])
+        xs = test_x.detach().to(dtype=torch.float64, device=e.device).contiguous()
+        full = xs.shape[0] <= FULL_COV_MAX_T
+        mean, var, cov = e.exact_predict(xs, t.X, ls, sf2, s2, r["factors"], kernel=t.kernel, pred_noise=pred_noise, full_cov=full)
+        return MultivariateNormal(mean, cov, variance=var, engine=self._dev_engine())
+
+    def sample_optimal_variational_hyper_dist(self, n_samples, input_dim, tune) -> Trace:
+        """``pm.sample(n_samples, tune=tune, chains=1)`` over the exact model; the trace has ``ls``, ``sig_f``, ``sig_n``."""
+        if int(input_dim) != self.data_dim:
+            raise ValueError("input_dim %d does not match the training inputs (%d)" % (input_dim, self.data_dim))
+        seed = None if self._seed is None else self._seed + self._n_hmc_calls
+        self._n_hmc_calls += 1
+        return sample_nuts(self._exact_target(), n_samples, tune, seed=seed)
+
+    def train_model(self):
+        """50 tuning + 10 draws (reference models/gpr_hmc.py:63-79).  Returns (trace_hyper, [step_size], [perf_time sum])."""
+        self.train()
+        self.likelihood.train()
+        trace_hyper = self.sample_optimal_variational_hyper_dist(10, self.data_dim, 50)
+        return (trace_hyper, [trace_hyper.get_sampler_stats('step_size')[0]],
+                [trace_hyper.get_sampler_stats('perf_counter_diff').sum()])
+
+
+def _gpr_full_mixture(model, test_x, trace_hyper):
+    """full_mixture_posterior_predictive of reference models/gpr_hmc.py:84-119: one exact predictive per draw; sig_n^2 < 1e-4 ->
+    sig_n = 0.01 in the trace row itself; a predictive whose cholesky(cov + 1e-2 I) fails is skipped with "Not psd for sample i"."""
+    preds = []
+    for i in range(len(trace_hyper)):
+        hyper_sample = trace_hyper[i]
+        model.train()
+        model.likelihood.train()
+        if hyper_sample['sig_n'] ** 2 < 1e-4:
+            hyper_sample['sig_n'] = 0.01
+        model.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
+        model.covar_module.outputscale = hyper_sample['sig_f'] ** 2
+        model.covar_module.base_kernel.lengthscale = hyper_sample['ls']
+        with torch.no_grad():
+            model.eval()
+            model.likelihood.eval()
+            try:
+                pred = model.likelihood(model(test_x))
+                if not pred.is_psd(1e-2):
+                    raise RuntimeError("predictive covariance not positive definite")
+                preds.append(pred)
+            except SgpTimeoutError:
+                raise
+            except (RuntimeError, NotPositiveDefiniteError):
+                print('Not psd for sample ' + str(i))
+    return preds
+
+
 def full_mixture_posterior_predictive(model, test_x, trace_hyper):
     """One predictive per joint draw, each with THAT draw's Z (reference models/all_in_HMC.py:84-119): a draw with
     sig_n^2 < 1e-4 gets sig_n = 0.01 (as in the reference, the trace row itself is changed); a predictive whose covariance fails
     cholesky(cov + 1e-5 I) is skipped with "Not psd for sample i".  The model is left at the last draw, Z included.
     Batched through sgp_mixture_predict_zs (eight draws per chain of launches, each with its own Z); the per-draw loop below is
-    the fallback where that does not apply (test double, several ranks, T beyond the full-covariance limit)."""
+    the fallback where that does not apply (test double, several ranks, T beyond the full-covariance limit).
+    For a ``GPR_HMC`` model: the exact predictive per draw (reference models/gpr_hmc.py:84-119, ``_gpr_full_mixture``)."""
+    if isinstance(model, GPR_HMC):
+        return _gpr_full_mixture(model, test_x, trace_hyper)
     for i in range(len(trace_hyper)):
         if trace_hyper[i]['sig_n'] ** 2 < 1e-4:
             trace_hyper[i]['sig_n'] = 0.01

@@ -713,6 +713,41 @@ int sgp_mixture_predict_zs(const double* X, int64_t ldx, const double* y, int64_
 int sgp_svgp_predict(const double* Xs, int64_t ldxs, int64_t T, const double* Z, int64_t ldz, const double* inv_ls,
                      double sf2, double jitter, const double* m, const double* LS, int M, int d, int kernel_id,
                      double* mean, double* var, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+/* ---- exact GP marginal likelihood (reference models/gpr_hmc.py:43-59: pm.gp.Marginal over sig_f^2 ExpQuad(ls), noise sig_n) ----
+ * F = log N(y | 0, A), A = K(X, X) + s2 I (no jitter: WhiteNoise(sig_n) adds s2 to the diagonal and nothing else).
+ *   1 <= N <= SGP_MAX_INDUCING, 1 <= d <= SGP_MAX_DIM, kernel_id 0..2 (SGP_KERNEL_COMPOSITE -> SGP_ERR_ARG), sf2 > 0, s2 >= 0;
+ *   anything else is refused before anything is enqueued (SGP_ERR_ARG / SGP_ERR_DIM / SGP_ERR_WORKSPACE).
+ *   out (DEVICE, 4 doubles) = [F, y^T A^-1 y, log|A|, tr A^-1]
+ *   grads (DEVICE, d + 2 doubles, with_grad != 0) = [dF/dls_1..d | dF/dsf2 | dF/ds2], dF/dls in sgp_kuu_bwd's convention (the
+ *     lengthscale itself, not its reciprocal)
+ *   factors (DEVICE, sgp_exact_factors_len(N) doubles, or NULL) = [L^-1 (Np x Np, Np = N rounded up to 128, lower triangle,
+ *     identity-padded, row-major) | alpha = A^-1 y (Np, zero-padded)]: opaque, what sgp_exact_predict consumes
+ *   info (DEVICE int, cleared by the call): the status word of sgp_kuu_factor_ex on A -- 0, k > 0 (A numerically not positive
+ *     definite at k, including the context's conditioning gate: SGP_OPT_COND_LIMIT, default 1e13), or SGP_INFO_TIMEOUT.  When it
+ *     is not 0 the outputs are meaningless; it is never an error return.
+ * Accuracy: A is factored through the explicit inverse, so F carries ~cond(A) 2^-53 relative error in y^T A^-1 y and the gradient
+ * ~cond(A) 2^-53 relative to its largest entry -- 1e-10 (|F| + N) and 1e-8 max|g| hold up to cond(A) ~ 1e8.  Every sum runs in a
+ * fixed order: the same bits on every call and every stream.  The gradient forms the lower-triangle tiles of A^-1 = L^-T L^-1 on
+ * the matrix cores and folds each into the d + 1 sums in place: A^-1 is never written to memory (N^3 / 3 flops + N^2 d).       */
+size_t sgp_exact_workspace_bytes(int64_t N, int d, int with_grad);
+size_t sgp_exact_factors_len(int64_t N);
+int sgp_exact_eval(const double* X, int64_t ldx, const double* y, int64_t N, int d, const double* inv_ls, double sf2, double s2,
+                   int kernel_id, int with_grad, double* out, double* grads, double* factors, int* info, void* ws, size_t ws_bytes,
+                   sgp_stream_t stream);
+int sgp_ctx_exact_eval(sgp_ctx* ctx, const double* X, int64_t ldx, const double* y, int64_t N, int d, const double* inv_ls, double sf2,
+                       double s2, int kernel_id, int with_grad, double* out, double* grads, double* factors, int* info, void* ws,
+                       size_t ws_bytes, sgp_stream_t stream);
+/* exact posterior predictive at T rows Xs from `factors` of sgp_exact_eval at the same (X, theta):
+ *   mean = K*X alpha ; var = k** - colsum(V^2) (+ s2 if pred_noise), V = L^-1 K_X* ; cov (T x T, optional, may be NULL; T <= 32768 as
+ *   for sgp_predict) = K** - V^T V (+ s2 I).  var may be NULL.                                                                      */
+size_t sgp_exact_predict_workspace_bytes(int64_t T, int64_t N, int d, int want_cov);
+int sgp_exact_predict(const double* Xs, int64_t ldxs, int64_t T, const double* X, int64_t ldx, int64_t N, int d, const double* inv_ls,
+                      double sf2, double s2, const double* factors, int kernel_id, int pred_noise, double* mean, double* var, double* cov,
+                      void* ws, size_t ws_bytes, sgp_stream_t stream);
+int sgp_ctx_exact_predict(sgp_ctx* ctx, const double* Xs, int64_t ldxs, int64_t T, const double* X, int64_t ldx, int64_t N, int d,
+                          const double* inv_ls, double sf2, double s2, const double* factors, int kernel_id, int pred_noise, double* mean,
+                          double* var, double* cov, void* ws, size_t ws_bytes, sgp_stream_t stream);
+
 /* host utility: n-point Gauss-Hermite rule for the standard normal (sum w_i f(x_i) ~ E f(N(0,1))) */
 int sgp_gauss_hermite(int n, double* x, double* w);
 
