@@ -6,8 +6,15 @@ d = 8, M = 1024 inducing points, RBF-ARD, fp64.  A "step" is ONE evaluation of t
 (pass 1 over the row shards + one all-reduce of [Phi|b|yy|kappa] + the O(M^3) tail).  With --gpus G the
 N rows are split into G contiguous shards (strong scaling: the job is fixed, one rank per GPU over RCCL).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description).  Extra keys:
+Prints ONE JSON line on rank 0 (see the driver contract in the task description).  A plain run sets up, warms up, times the
+--steps evaluations, times max(2, steps // 2) value + gradient evaluations after one warm-up, writes --dump-outputs and prints the
+line: the headline (metric, value, unit, ms_per_step, ...), the returned F, the configuration and these extra keys:
   leapfrog_per_s    : value + gradient wrt (lengthscales, sig_f, sig_n) evaluations / s, same run, same data
+  config            : workload, theta, ranks and devices (several ranks: asserted distinct, over RCCL), contraction, evaluation order,
+                      the streaming-order guard's counters over the timed evaluations
+
+--full measures, after the same timed steps, what the headline does not need:
+  config.allreduce_ms : several ranks: the packed all-reduce of an evaluation, timed alone
   roofline          : the dominant kernel of the timed evaluations: `i8_syrk_tile_kernel` (pass-1 contraction on the integer
                       matrix cores, what evaluations of big shards run) against the dense int8 peak, with the
                       fp64-equivalent rate beside it; `roofline_fp64_contraction` is `syrk_tile_kernel` (the fp64 contraction:
@@ -19,6 +26,9 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task description)
                       (PMC passes, tools/profile_round.sh), traffic_ratio = traffic / the kernel's algorithmic bytes;
                       mfma_pipe_busy = SQ_VALU_MFMA_BUSY_CYCLES / (4 SQ_BUSY_CU_CYCLES) from the newest profiles/*_pmc_sq_counters.csv
   roofline_leapfrog : the same for the dominant kernel of the reverse pass, `kbar_contract_kernel` (2 N M^2 flop)
+  assembly, assembly_digits : the kernel assembly of pass 1 against HBM bandwidth
+  config.streaming_guard.whitened_order / .extended_order, leapfrog_per_s_trained_theta : one rank: the evaluation orders the guard
+                      falls back to, and NUTS-target leapfrogs at the trained theta of C5
   cpu_baseline      : the oracle's PyMC3-op-order restatement timed on this box's host cores (rank 0, N=1 only): value
                       only on ALL N rows in 65 536-row chunks (--cpu-fit: two sample sizes, fixed + per-row
                       cost fitted and evaluated at N), and value + autograd gradient fitted from two samples (its graph does
@@ -191,12 +201,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", dest="n", type=int, default=N_TOTAL)
     ap.add_argument("--inducing", dest="m", type=int, default=M_IND)
-    ap.add_argument("--cpu-sample", type=int, default=200_000, help="rows of the larger CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: kernel rooflines, the all-reduce alone, "
+                         "the guard's fallback orders, leapfrogs at the trained theta and the CPU baseline (see the module docstring)")
+    ap.add_argument("--cpu-sample", type=int, default=200_000, help="with --full: rows of the larger CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-full", dest="cpu_full", action="store_true", default=True,
-                    help="time the CPU baseline's value-only evaluation on ALL N rows in 65 536-row chunks (SURVEY section 8d; ~80-110 s "
-                         "at C5; the default since round 4)")
+                    help="with --full: time the CPU baseline's value-only evaluation on ALL N rows in 65 536-row chunks (SURVEY "
+                         "section 8d; ~80-110 s at C5; the default since round 4)")
     ap.add_argument("--cpu-fit", dest="cpu_full", action="store_false",
-                    help="fit the CPU baseline from two samples (--cpu-sample rows and half of it) instead of timing all N rows")
+                    help="with --full: fit the CPU baseline from two samples (--cpu-sample rows and half of it) instead of timing all N rows")
     ap.add_argument("--ls", type=float, default=LS, help="lengthscale of the timed theta (default: SURVEY section 8d's 2.0; tests use a long "
                                                          "one to drive the streaming-order guard on several ranks)")
     ap.add_argument("--sig-n", type=float, default=SN, help="noise standard deviation of the timed theta (default 0.3)")
@@ -287,71 +300,72 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, last)
 
-    # dominant kernels, timed alone: the library records HIP events on the launch stream right around them
-    # (include/sgp.h: sgp_timing_*; slot 0 kernel assembly, 1 pass-1 contraction, 2 pass-2 contraction)
-    import ctypes
     n_local = hi - lo
-    eng.lib.sgp_timing_enable(1)
-    kfu = eng.kfu_buffer(n_local, args.m)
-    prev_mode = eng.lib.sgp_set_contraction(0)  # the fp64 contraction and the fp64 assembly, timed for the record (roofline_fp64_contraction)
-    packed = eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", kfu=kfu)
-    Kuu = eng.kuu(Zd, ls, sf2, JITTER, "rbf")
-    adj = eng.bound(Kuu, packed, s2, args.n, with_adjoints=True)
-    torch.cuda.synchronize(dev)
-    reps = max(3, min(10, args.steps))
-    ms = {0: [], 1: [], 2: []}
-    for _ in range(reps):
-        eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed, kfu=kfu)
-        eng.suffstats_bwd(Xd, yd, Zd, ls, sf2, adj["Phibar"], adj["bbar"], -1.0 / (2.0 * s2), "rbf", kfu=kfu)
-        for slot in ms:
-            t = ctypes.c_float(0.0)
-            assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
-            ms[slot].append(t.value)
-    eng.lib.sgp_set_contraction(prev_mode)
-    # pass 1 of a value + gradient evaluation as the timed leapfrogs run it: on the integer cores the assembly writes the fp64 block too
-    mg = {0: [], 1: []}
-    for _ in range(reps):
-        eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed, kfu=kfu)
-        for slot in mg:
-            t = ctypes.c_float(0.0)
-            assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
-            mg[slot].append(t.value)
-    int8_grad = eng.lib.sgp_contraction_last() == 1
-    both_ms, i8g_ms = (sorted(v)[len(v) // 2] for v in (mg[0], mg[1]))
-    del kfu
-    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
-    assemble_ms, syrk_ms, kbar_ms = med[0], med[1], med[2]
-    # pass 1 as the timed evaluations (value only, nobody keeps K'_fu) run it: on big shards the library contracts on the INTEGER
-    # matrix cores (include/sgp.h: sgp_set_contraction; csrc/sgp_suffstats_i8.hip) -- same statistics, different dominant kernel
-    mv = {0: [], 1: []}
-    for _ in range(reps):
-        eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed)
-        for slot in mv:
-            t = ctypes.c_float(0.0)
-            assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
-            mv[slot].append(t.value)
-    int8_eval = eng.lib.sgp_contraction_last() == 1
-    eng.lib.sgp_timing_enable(0)
-    digits_ms, i8_ms = (sorted(v)[len(v) // 2] for v in (mv[0], mv[1]))
-    Mp = (args.m + 127) // 128 * 128
-    kfu_bytes = 8.0 * ((n_local + 255) // 256 * 256) * Mp
-    syrk_flops = float(n_local) * args.m * (args.m + 1)            # the contraction's own work: lower triangle, 2 flop / MAC
-    kbar_flops = 2.0 * float(n_local) * args.m * args.m             # Kbar_uf = 2 Phibar K_uf
-    wfwd = algorithmic_flops_fwd(n_local, args.m, DIM)
-    default_cfg = (args.n, args.m, world) == (N_TOTAL, M_IND, 1)
-    syrk_traffic, syrk_file = pmc_traffic("sgp::syrk_tile_kernel<") if default_cfg else (None, None)
-    kbar_traffic, kbar_file = pmc_traffic("kbar_contract_kernel") if default_cfg else (None, None)
-    syrk_tf = syrk_flops / (syrk_ms * 1e-3) / 1e12
-    i8_traffic, i8_file = pmc_traffic("sgp::i8_syrk_tile_kernel<6, false>(") if default_cfg else (None, None)
-    i8_busy, i8_busy_file = pmc_mfma_busy("sgp::i8_syrk_tile_kernel<6, false>(") if default_cfg else (None, None)
-    syrk_busy, _ = pmc_mfma_busy("sgp::syrk_tile_kernel<") if default_cfg else (None, None)
-    kbar_busy, _ = pmc_mfma_busy("sgp::kbar_contract_kernel<") if default_cfg else (None, None)
-    q_bytes = 7.0 * ((n_local + 255) // 256 * 256) * Mp          # digit planes: 7 bytes per element of K'_fu
-    i8_ops = 28.0 * syrk_flops                                   # 28 digit-pair products per fp64 product, 2 op per MAC
-    i8_tops = i8_ops / (i8_ms * 1e-3) / 1e12
-    kbar_tf = kbar_flops / (kbar_ms * 1e-3) / 1e12
-    note = ("HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE (x2 gfx950 correction) + WRITE_SIZE in separate passes "
-            "(tools/profile_round.sh), read from %s; not collected in this run")
+    if args.full:
+        # dominant kernels, timed alone: the library records HIP events on the launch stream right around them
+        # (include/sgp.h: sgp_timing_*; slot 0 kernel assembly, 1 pass-1 contraction, 2 pass-2 contraction)
+        import ctypes
+        eng.lib.sgp_timing_enable(1)
+        kfu = eng.kfu_buffer(n_local, args.m)
+        prev_mode = eng.lib.sgp_set_contraction(0)  # the fp64 contraction and the fp64 assembly, timed for the record (roofline_fp64_contraction)
+        packed = eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", kfu=kfu)
+        Kuu = eng.kuu(Zd, ls, sf2, JITTER, "rbf")
+        adj = eng.bound(Kuu, packed, s2, args.n, with_adjoints=True)
+        torch.cuda.synchronize(dev)
+        reps = max(3, min(10, args.steps))
+        ms = {0: [], 1: [], 2: []}
+        for _ in range(reps):
+            eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed, kfu=kfu)
+            eng.suffstats_bwd(Xd, yd, Zd, ls, sf2, adj["Phibar"], adj["bbar"], -1.0 / (2.0 * s2), "rbf", kfu=kfu)
+            for slot in ms:
+                t = ctypes.c_float(0.0)
+                assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
+                ms[slot].append(t.value)
+        eng.lib.sgp_set_contraction(prev_mode)
+        # pass 1 of a value + gradient evaluation as the timed leapfrogs run it: on the integer cores the assembly writes the fp64 block too
+        mg = {0: [], 1: []}
+        for _ in range(reps):
+            eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed, kfu=kfu)
+            for slot in mg:
+                t = ctypes.c_float(0.0)
+                assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
+                mg[slot].append(t.value)
+        int8_grad = eng.lib.sgp_contraction_last() == 1
+        both_ms, i8g_ms = (sorted(v)[len(v) // 2] for v in (mg[0], mg[1]))
+        del kfu
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        assemble_ms, syrk_ms, kbar_ms = med[0], med[1], med[2]
+        # pass 1 as the timed evaluations (value only, nobody keeps K'_fu) run it: on big shards the library contracts on the INTEGER
+        # matrix cores (include/sgp.h: sgp_set_contraction; csrc/sgp_suffstats_i8.hip) -- same statistics, different dominant kernel
+        mv = {0: [], 1: []}
+        for _ in range(reps):
+            eng.suffstats(Xd, yd, Zd, ls, sf2, "rbf", out=packed)
+            for slot in mv:
+                t = ctypes.c_float(0.0)
+                assert eng.lib.sgp_timing_last_ms(slot, ctypes.byref(t)) == 0
+                mv[slot].append(t.value)
+        int8_eval = eng.lib.sgp_contraction_last() == 1
+        eng.lib.sgp_timing_enable(0)
+        digits_ms, i8_ms = (sorted(v)[len(v) // 2] for v in (mv[0], mv[1]))
+        Mp = (args.m + 127) // 128 * 128
+        kfu_bytes = 8.0 * ((n_local + 255) // 256 * 256) * Mp
+        syrk_flops = float(n_local) * args.m * (args.m + 1)            # the contraction's own work: lower triangle, 2 flop / MAC
+        kbar_flops = 2.0 * float(n_local) * args.m * args.m             # Kbar_uf = 2 Phibar K_uf
+        wfwd = algorithmic_flops_fwd(n_local, args.m, DIM)
+        default_cfg = (args.n, args.m, world) == (N_TOTAL, M_IND, 1)
+        syrk_traffic, syrk_file = pmc_traffic("sgp::syrk_tile_kernel<") if default_cfg else (None, None)
+        kbar_traffic, kbar_file = pmc_traffic("kbar_contract_kernel") if default_cfg else (None, None)
+        syrk_tf = syrk_flops / (syrk_ms * 1e-3) / 1e12
+        i8_traffic, i8_file = pmc_traffic("sgp::i8_syrk_tile_kernel<6, false>(") if default_cfg else (None, None)
+        i8_busy, i8_busy_file = pmc_mfma_busy("sgp::i8_syrk_tile_kernel<6, false>(") if default_cfg else (None, None)
+        syrk_busy, _ = pmc_mfma_busy("sgp::syrk_tile_kernel<") if default_cfg else (None, None)
+        kbar_busy, _ = pmc_mfma_busy("sgp::kbar_contract_kernel<") if default_cfg else (None, None)
+        q_bytes = 7.0 * ((n_local + 255) // 256 * 256) * Mp          # digit planes: 7 bytes per element of K'_fu
+        i8_ops = 28.0 * syrk_flops                                   # 28 digit-pair products per fp64 product, 2 op per MAC
+        i8_tops = i8_ops / (i8_ms * 1e-3) / 1e12
+        kbar_tf = kbar_flops / (kbar_ms * 1e-3) / 1e12
+        note = ("HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE (x2 gfx950 correction) + WRITE_SIZE in separate passes "
+                "(tools/profile_round.sh), read from %s; not collected in this run")
     # the binary these numbers come from: sha256 over every kernel source / header / linker script (build.py), so a traffic
     # figure read from profiles/ can be matched to the build it was collected on
     try:
@@ -362,7 +376,7 @@ def main():
 
     devices = [torch.cuda.get_device_properties(dev).name + " #%d" % local_rank]
     device_check = "single rank"
-    allreduce_ms = None
+    allreduce_ms = allreduce_bytes = None
     if world > 1:
         share = os.environ.get("SGP_BENCH_SHARE_GPU") == "1"
         props = torch.cuda.get_device_properties(dev)
@@ -382,19 +396,20 @@ def main():
             if backends != ["nccl"]:
                 raise SystemExit("bench.py: collectives must run over RCCL (backend 'nccl'), got %r" % (backends,))
             device_check = "distinct device per rank, backend nccl (RCCL), world size %d" % world
-        # THE exchange of an evaluation, timed alone: all-reduce of [lower triangle of Phi | b | yy | kappa]
-        tri = torch.zeros(args.m * (args.m + 1) // 2 + args.m + 2, dtype=torch.float64, device=dev)
-        for _ in range(3):
-            dist.all_reduce(tri)
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(20):
-            dist.all_reduce(tri)
-        torch.cuda.synchronize(dev)
-        t = torch.tensor([(time.perf_counter() - t0) / 20], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        allreduce_ms = 1e3 * float(t.item())
-        allreduce_bytes = tri.numel() * 8
+        if args.full:
+            # THE exchange of an evaluation, timed alone: all-reduce of [lower triangle of Phi | b | yy | kappa]
+            tri = torch.zeros(args.m * (args.m + 1) // 2 + args.m + 2, dtype=torch.float64, device=dev)
+            for _ in range(3):
+                dist.all_reduce(tri)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                dist.all_reduce(tri)
+            torch.cuda.synchronize(dev)
+            t = torch.tensor([(time.perf_counter() - t0) / 20], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            allreduce_ms = 1e3 * float(t.item())
+            allreduce_bytes = tri.numel() * 8
 
     res = {
         "metric": "ELBO evals/sec", "value": evals_per_s, "unit": "evals/s", "n_gpus": world, "steps": args.steps,
@@ -404,7 +419,7 @@ def main():
                                % (args.n, DIM, args.m, world), "N": args.n, "M": args.m, "d": DIM, "jitter": JITTER,
                    "theta": {"ls": LS, "sig_f": SF, "sig_n": SN}, "ranks": world, "collective_backend": backend if world > 1 else None,
                    "devices": devices, "device_check": device_check, "rows_per_rank": n_local,
-                   "allreduce_ms": allreduce_ms, "allreduce_bytes": allreduce_bytes if world > 1 else None,
+                   "allreduce_ms": allreduce_ms, "allreduce_bytes": allreduce_bytes,
                    "collectives_per_eval": coll_per_eval, "source_digest": source_digest,
                    "evaluation_order": ("single launch (M <= 128)" if cb._small_ok(args.m) else
                                         "whitened (A = L^-1 K_uf materialised, B = I + A A^T / s2; pass 2 from the factored adjoint)"
@@ -412,63 +427,68 @@ def main():
                                         "streaming (Phi = K_uf K_fu over the row shards, W = L^-1 Phi L^-T in the replicated tail)")},
         "leapfrog_per_s": leap_per_s, "ms_per_leapfrog": 1e3 / leap_per_s,
         "F": last["F"], "F_per_datum": last["F"] / args.n,
-        "roofline": None,
-        "roofline_fp64_contraction": {
-                     "bound": "mfma", "kernel": "sgp::syrk_tile_kernel (pass-1 contraction on the fp64 matrix cores: sgp_set_contraction(0), and shards below the "
-                                                "integer path's threshold)",
-                     "achieved": syrk_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": syrk_tf / FP64_MATRIX_PEAK_TFLOPS,
-                     "ms": syrk_ms, "mfma_pipe_busy": syrk_busy, "algorithmic_flops": syrk_flops, "algorithmic_flops_formula": "N M (M + 1): lower triangle of Phi, 2 flop per MAC",
-                     "algorithmic_bytes": kfu_bytes, "traffic": syrk_traffic,
-                     "traffic_ratio": (syrk_traffic / kfu_bytes) if syrk_traffic else None,
-                     "traffic_note": (note % syrk_file) if syrk_file else None,
-                     "pass1": {"kernels": "kfu_assemble_kernel + syrk_tile_kernel", "ms": assemble_ms + syrk_ms, "algorithmic_flops": wfwd,
-                               "achieved": wfwd / ((assemble_ms + syrk_ms) * 1e-3) / 1e12, "frac": wfwd / ((assemble_ms + syrk_ms) * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
-                               "note": "SURVEY section 8d W_fwd (contraction + b + scaled distances) over both kernels of pass 1"},
-                     "materialised_note": "K'_fu is written once (HBM-write bound assembly) and read back by the contraction: a fused kernel would "
-                                          "move 80.5 MB per evaluation instead of ~55 GB, but measured 53 ms (fp64 VALU exp() and MFMA share the datapath)"},
-        "roofline_leapfrog": {"bound": "mfma", "kernel": "sgp::kbar_contract_kernel (pass-2 contraction + derivative epilogue)",
-                              "achieved": kbar_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": kbar_tf / FP64_MATRIX_PEAK_TFLOPS,
-                              "ms": kbar_ms, "mfma_pipe_busy": kbar_busy, "algorithmic_flops": kbar_flops, "algorithmic_flops_formula": "2 N M^2 (Kbar_uf = 2 Phibar K_uf)",
-                              "algorithmic_bytes": kfu_bytes, "traffic": kbar_traffic,
-                              "traffic_ratio": (kbar_traffic / kfu_bytes) if kbar_traffic else None,
-                              "traffic_note": (note % kbar_file) if kbar_file else None},
-        "assembly": {"bound": "hbm", "kernel": "sgp::kfu_assemble_kernel<8,0>", "ms": assemble_ms,
-                     "achieved": kfu_bytes / (assemble_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                     "frac": kfu_bytes / (assemble_ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes": kfu_bytes},
     }
-    if int8_eval:
-        # the dominant kernel of the timed evaluations: the contraction on the integer matrix cores.  Its roofline is the int8
-        # one; the fp64-equivalent rate (the work it REPLACES over its time) is what compares with the fp64 contraction above.
-        res["roofline"] = {
-            "bound": "mfma", "kernel": "sgp::i8_syrk_tile_kernel (pass-1 contraction of the timed evaluations: K'_fu as 7 balanced 8-bit digit "
-                                       "planes, 28 exact int32 digit-pair products on v_mfma_i32_32x32x32_i8, one fp64 fold per split)",
-            "achieved": i8_tops, "peak": INT8_MATRIX_PEAK_TOPS, "unit": "TOP/s", "frac": i8_tops / INT8_MATRIX_PEAK_TOPS, "ms": i8_ms,
-            "algorithmic_ops": i8_ops, "algorithmic_ops_formula": "28 N M (M + 1): 28 of the 49 digit pairs of every fp64 product, 2 op per MAC",
-            "sustained_peak": INT8_SUSTAINED_TOPS, "frac_of_sustained_peak": i8_tops / INT8_SUSTAINED_TOPS,
-            "sustained_peak_note": "back-to-back v_mfma_i32_32x32x32_i8 on full-entropy operands, no memory traffic: the chip clocks down to "
-                                   "~1.78 GHz (profiles/r03_i8_rates.txt) -- power, not issue slots, bounds this kernel",
-            "fp64_equivalent": {"achieved": syrk_flops / (i8_ms * 1e-3) / 1e12, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                "frac": syrk_flops / (i8_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
-                                "note": "N M (M + 1) flop of the fp64 contraction it replaces over its own time; > 1 = faster than the fp64 matrix peak allows"},
-            "mfma_pipe_busy": i8_busy, "mfma_pipe_busy_note": ("SQ_VALU_MFMA_BUSY_CYCLES / (4 SQ_BUSY_CU_CYCLES) from %s (PMC passes, tools/profile_sq.sh); "
-                                                                 "not collected in this run" % i8_busy_file) if i8_busy_file else None,
-            "algorithmic_bytes": q_bytes, "traffic": i8_traffic, "traffic_ratio": (i8_traffic / q_bytes) if i8_traffic else None,
-            "traffic_note": (note % i8_file) if i8_file else None,
-            "pass1": {"kernels": "kfu_digits_kernel + i8_syrk_tile_kernel", "ms": digits_ms + i8_ms, "fp64_pass1_ms": assemble_ms + syrk_ms},
-            "pass1_of_a_leapfrog": ({"kernels": "kfu_digits_kernel<.., true> (fp64 block + digit planes) + i8_syrk_tile_kernel", "assembly_ms": both_ms,
-                                     "contraction_ms": i8g_ms, "ms": both_ms + i8g_ms} if int8_grad else None),
-            "accuracy": "as the fp64 contraction: |K' - q 2^-54| <= 2^-55, digit products exact, dropped pairs < 6 x 2^-54 per product and "
-                        "zero-mean; 2.4-2.8e-16 of max |Phi| against long double (tests/test_int8_contraction.py, tools/i8_syrk_proto.hip)"}
+    # the contraction the timed evaluations ran: the library's own rule for a value-only pass 1 on this shard (no GPU work)
+    if eng.would_use_i8(n_local, args.m):
         res["config"]["contraction"] = "int8 digit planes on the integer matrix cores (error-free split of K'_fu, fp64 result)"
         res["dtype_note"] = ("fp64 kernel values, statistics, factorizations and gradients; the pass-1 contraction multiplies exact 8-bit digits of the "
                              "fp64 kernel values on the integer matrix cores (int32 sums, folded to fp64): as accurate as the fp64 contraction, not a reduced precision")
-        res["assembly_digits"] = {"bound": "valu", "kernel": "sgp::kfu_digits_kernel<8,0>", "ms": digits_ms,
-                                  "achieved": q_bytes / (digits_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                                  "frac": q_bytes / (digits_ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes": q_bytes,
-                                  "note": "exp + 53-bit fixed-point conversion + byte transposition per element: fp64 / integer VALU bound, not HBM bound"}
     else:
-        res["roofline"] = dict(res["roofline_fp64_contraction"])
         res["config"]["contraction"] = "fp64 matrix cores"
+    if args.full:
+        res.update({
+            "roofline_fp64_contraction": {
+                         "bound": "mfma", "kernel": "sgp::syrk_tile_kernel (pass-1 contraction on the fp64 matrix cores: sgp_set_contraction(0), and shards below the "
+                                                    "integer path's threshold)",
+                         "achieved": syrk_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": syrk_tf / FP64_MATRIX_PEAK_TFLOPS,
+                         "ms": syrk_ms, "mfma_pipe_busy": syrk_busy, "algorithmic_flops": syrk_flops, "algorithmic_flops_formula": "N M (M + 1): lower triangle of Phi, 2 flop per MAC",
+                         "algorithmic_bytes": kfu_bytes, "traffic": syrk_traffic,
+                         "traffic_ratio": (syrk_traffic / kfu_bytes) if syrk_traffic else None,
+                         "traffic_note": (note % syrk_file) if syrk_file else None,
+                         "pass1": {"kernels": "kfu_assemble_kernel + syrk_tile_kernel", "ms": assemble_ms + syrk_ms, "algorithmic_flops": wfwd,
+                                   "achieved": wfwd / ((assemble_ms + syrk_ms) * 1e-3) / 1e12, "frac": wfwd / ((assemble_ms + syrk_ms) * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
+                                   "note": "SURVEY section 8d W_fwd (contraction + b + scaled distances) over both kernels of pass 1"},
+                         "materialised_note": "K'_fu is written once (HBM-write bound assembly) and read back by the contraction: a fused kernel would "
+                                              "move 80.5 MB per evaluation instead of ~55 GB, but measured 53 ms (fp64 VALU exp() and MFMA share the datapath)"},
+            "roofline_leapfrog": {"bound": "mfma", "kernel": "sgp::kbar_contract_kernel (pass-2 contraction + derivative epilogue)",
+                                  "achieved": kbar_tf, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": kbar_tf / FP64_MATRIX_PEAK_TFLOPS,
+                                  "ms": kbar_ms, "mfma_pipe_busy": kbar_busy, "algorithmic_flops": kbar_flops, "algorithmic_flops_formula": "2 N M^2 (Kbar_uf = 2 Phibar K_uf)",
+                                  "algorithmic_bytes": kfu_bytes, "traffic": kbar_traffic,
+                                  "traffic_ratio": (kbar_traffic / kfu_bytes) if kbar_traffic else None,
+                                  "traffic_note": (note % kbar_file) if kbar_file else None},
+            "assembly": {"bound": "hbm", "kernel": "sgp::kfu_assemble_kernel<8,0>", "ms": assemble_ms,
+                         "achieved": kfu_bytes / (assemble_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                         "frac": kfu_bytes / (assemble_ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes": kfu_bytes},
+        })
+        if int8_eval:
+            # the dominant kernel of the timed evaluations: the contraction on the integer matrix cores.  Its roofline is the int8
+            # one; the fp64-equivalent rate (the work it REPLACES over its time) is what compares with the fp64 contraction above.
+            res["roofline"] = {
+                "bound": "mfma", "kernel": "sgp::i8_syrk_tile_kernel (pass-1 contraction of the timed evaluations: K'_fu as 7 balanced 8-bit digit "
+                                           "planes, 28 exact int32 digit-pair products on v_mfma_i32_32x32x32_i8, one fp64 fold per split)",
+                "achieved": i8_tops, "peak": INT8_MATRIX_PEAK_TOPS, "unit": "TOP/s", "frac": i8_tops / INT8_MATRIX_PEAK_TOPS, "ms": i8_ms,
+                "algorithmic_ops": i8_ops, "algorithmic_ops_formula": "28 N M (M + 1): 28 of the 49 digit pairs of every fp64 product, 2 op per MAC",
+                "sustained_peak": INT8_SUSTAINED_TOPS, "frac_of_sustained_peak": i8_tops / INT8_SUSTAINED_TOPS,
+                "sustained_peak_note": "back-to-back v_mfma_i32_32x32x32_i8 on full-entropy operands, no memory traffic: the chip clocks down to "
+                                       "~1.78 GHz (profiles/r03_i8_rates.txt) -- power, not issue slots, bounds this kernel",
+                "fp64_equivalent": {"achieved": syrk_flops / (i8_ms * 1e-3) / 1e12, "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                    "frac": syrk_flops / (i8_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
+                                    "note": "N M (M + 1) flop of the fp64 contraction it replaces over its own time; > 1 = faster than the fp64 matrix peak allows"},
+                "mfma_pipe_busy": i8_busy, "mfma_pipe_busy_note": ("SQ_VALU_MFMA_BUSY_CYCLES / (4 SQ_BUSY_CU_CYCLES) from %s (PMC passes, tools/profile_sq.sh); "
+                                                                     "not collected in this run" % i8_busy_file) if i8_busy_file else None,
+                "algorithmic_bytes": q_bytes, "traffic": i8_traffic, "traffic_ratio": (i8_traffic / q_bytes) if i8_traffic else None,
+                "traffic_note": (note % i8_file) if i8_file else None,
+                "pass1": {"kernels": "kfu_digits_kernel + i8_syrk_tile_kernel", "ms": digits_ms + i8_ms, "fp64_pass1_ms": assemble_ms + syrk_ms},
+                "pass1_of_a_leapfrog": ({"kernels": "kfu_digits_kernel<.., true> (fp64 block + digit planes) + i8_syrk_tile_kernel", "assembly_ms": both_ms,
+                                         "contraction_ms": i8g_ms, "ms": both_ms + i8g_ms} if int8_grad else None),
+                "accuracy": "as the fp64 contraction: |K' - q 2^-54| <= 2^-55, digit products exact, dropped pairs < 6 x 2^-54 per product and "
+                            "zero-mean; 2.4-2.8e-16 of max |Phi| against long double (tests/test_int8_contraction.py, tools/i8_syrk_proto.hip)"}
+            res["assembly_digits"] = {"bound": "valu", "kernel": "sgp::kfu_digits_kernel<8,0>", "ms": digits_ms,
+                                      "achieved": q_bytes / (digits_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                                      "frac": q_bytes / (digits_ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes": q_bytes,
+                                      "note": "exp + 53-bit fixed-point conversion + byte transposition per element: fp64 / integer VALU bound, not HBM bound"}
+        else:
+            res["roofline"] = dict(res["roofline_fp64_contraction"])
     res["config"]["streaming_guard"] = {
         "tolerance_per_datum": cb.streaming_tol, "estimate_per_datum": cb.last_estimate, "repeats_in_whitened_order": cb.n_guard_reruns,
         "direct_whitened_evaluations": cb.n_direct_whitened, "extended_order_evaluations": cb.n_extended,
@@ -483,7 +503,7 @@ def main():
                 "below half the tolerance -- 0, 0 and 0 = every timed step ran the streaming design"
                 % (cb.extended_level, 39 if cb.extended_level >= 2 else 34, cb.extended_range,
                    cb.extended_grad_range_lo if cb._bwd_lo_ok(args.m) else cb.extended_grad_range)}
-    if world == 1:
+    if args.full and world == 1:
         # what an evaluation costs where the guard sends it: the whitened (PyMC3) order on the same shard and theta, a few repetitions
         # outside the timed region (engine.suffstats_whitened_rows + suffstats_bwd_factored)
         wb = ggp_amd.CollapsedBound(Xd, yd, kernel="rbf", jitter=JITTER, engine=eng, form="whitened")
@@ -561,7 +581,7 @@ def main():
                     "four evaluations each; `parity` (default): every gradient holds 1e-6 -- since round 6 in the extended order with both words "
                     "of a double-double Phibar while the trailing word's correction stays small (13.4 / s in the whitened order through round 5); "
                     "`sampler` = HmcTarget(gradient='sampler'): the leading word only"}
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         res["cpu_baseline"] = cpu_baseline(X, y, Z, min(args.cpu_sample, args.n), args.cpu_full)
     if rank == 0:
         print(json.dumps(res))

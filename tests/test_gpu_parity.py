@@ -971,7 +971,9 @@ def test_two_ranks_share_the_gpu_real_engine_matches_one_rank():
     import sys
     from conftest import ROOT
     rows = 131072
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--rows", str(rows)]
+    # --full: config.allreduce_ms (the packed all-reduce timed alone) is one of the extra measurements
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--rows", str(rows),
+            "--full"]
     one = subprocess.run(base, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     r1 = json.loads(one.stdout.strip().splitlines()[-1])
@@ -1033,6 +1035,38 @@ def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
     g = np.load(str(out / "grad_ls.npy"))
     assert g.shape == (res["config"]["d"],) and np.isfinite(g).all()
     assert sum(os.path.getsize(str(out / f)) for f in os.listdir(out)) < 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_extra_measurements_to_the_same_timed_steps():
+    """A plain bench.py run prints the headline, leapfrog_per_s, F and the configuration only; --full times the same steps on the
+    same seeded inputs and adds the kernel rooflines, the guard's fallback orders and the trained-theta leapfrogs (the CPU
+    baseline is skipped here: --cpu-sample 0)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--rows", "131072"]
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = runs["plain"], runs["full"]
+    moved = ("roofline", "roofline_fp64_contraction", "roofline_leapfrog", "assembly", "leapfrog_per_s_trained_theta", "cpu_baseline")
+    for res in (plain, full):
+        assert res["metric"] == "ELBO evals/sec" and res["unit"] == "evals/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+        assert res["steps"] == 2 and res["warmup"] == 1 and abs(res["ms_per_step"] - 1e3 / res["value"]) < 1e-9 * res["ms_per_step"]
+        assert res["leapfrog_per_s"] > 0 and res["config"]["contraction"].startswith("int8")
+        assert res["config"]["streaming_guard"]["repeats_in_whitened_order"] == 0
+    assert not any(k in plain for k in moved)
+    assert "whitened_order" not in plain["config"]["streaming_guard"] and plain["config"]["allreduce_ms"] is None
+    assert abs(full["F"] - plain["F"]) < 1e-12 * abs(plain["F"])
+    assert full["roofline"]["ms"] > 0 and full["roofline"]["kernel"].startswith("sgp::i8_syrk_tile_kernel")
+    assert full["roofline_fp64_contraction"]["ms"] > 0 and full["roofline_leapfrog"]["ms"] > 0 and full["assembly_digits"]["ms"] > 0
+    assert full["config"]["streaming_guard"]["whitened_order"]["ms_per_evaluation"] > 0
+    assert full["config"]["streaming_guard"]["extended_order"]["ms_per_leapfrog"] > 0
+    assert full["leapfrog_per_s_trained_theta"]["parity"] > 0 and "cpu_baseline" not in full
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ARGS=""
 for C in SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE; do
-  rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/sq_$C" -o run -- python3 bench.py --steps 2 --warmup 1 --cpu-sample 0 > /dev/null 2> "$OUT/sq_$C.err"
+  rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/sq_$C" -o run -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample 0 > /dev/null 2> "$OUT/sq_$C.err"
   ARGS="$ARGS $C=$OUT/sq_$C"
 done
 python3 tools/summarise_pmc.py "$OUT/pmc_sq_counters.csv" $ARGS
