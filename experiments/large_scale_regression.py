@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--hmc_samples", type=int, default=0, help="fixed-Z NUTS draws after training (0 = skip)")
     ap.add_argument("--hmc_tune", type=int, default=10)
     ap.add_argument("--hmc_gradient", choices=["parity", "sampler"], default="parity",
-                    help="core.HmcTarget: 'sampler' lets the extended evaluation order serve gradients as far as values (guarded regime)")
+                    help="targets.HmcTarget: 'sampler' lets the extended evaluation order serve gradients as far as values (guarded regime)")
     args = ap.parse_args()
 
     g = torch.Generator().manual_seed(0)

@@ -6,7 +6,7 @@ valid Python identifier: import it through the repo-root shim ``ggp_amd`` (``imp
 from ._lib import KERNEL_IDS, SgpLibraryError, SgpStatusError, load_library  # noqa: F401
 from .composite import (CO2_LOG_PRIOR_SD, CompositeBayesianSparseGPR_HMC, CompositeHmcTarget, CompositeKernel, Factor,  # noqa: F401
                         co2_kernel)
-from .core import CollapsedBound, ExactHmcTarget, HmcTarget, JointHmcTarget, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
+from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
 from . import datasets, experiment_tools  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
                       MultivariateNormal, RBFKernel, ScaleKernel, ZeroMean, settings)
@@ -14,6 +14,7 @@ from .hmc import NUTS, SplitMix, Trace, sample_nuts, sample_nuts_device  # noqa:
 from .metrics import nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
+from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must work without a GPU (build / symbol checks)

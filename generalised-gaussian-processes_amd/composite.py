@@ -21,7 +21,9 @@ import numpy as np
 import torch
 
 from ._lib import COMP_LEN
-from .core import CollapsedBound
+from .core import CollapsedBound, few_host_threads
+from .hmc import next_seed, sample_nuts, sample_nuts_device, trace_summary
+from .targets import as_floats, device_sampler_ok, in_range, single_launch_eval, single_launch_ok
 
 EXPQUAD, MATERN32, MATERN52, RATQUAD, PERIODIC = 0, 1, 2, 3, 4
 _FACTOR_IDS = {"expquad": EXPQUAD, "rbf": EXPQUAD, "matern32": MATERN32, "matern52": MATERN52, "ratquad": RATQUAD,
@@ -159,38 +161,32 @@ class CompositeHmcTarget:
                 "free": [(slot, self._ROLE_ID[role], sd) for (_, slot, role), sd in zip(self.params, self.sd)]}
 
     def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
-        """True when ``hmc.sample_nuts_device`` can run this target (single-launch path, at most 17 sampled parameters, and -- when
-        the run length is given -- a worst case inside the persistent kernel's counters, ``core.device_run_fits``)."""
-        from .core import device_run_fits
-        b = self.bound
-        ok = hasattr(b, "_small_ok") and hasattr(b.engine, "small_nuts") and b._small_ok(self.Z.shape[0]) and self.ndim <= 18
-        return ok and (n_draws_total is None or device_run_fits(int(b.X.shape[0]), n_draws_total, max_treedepth))
+        """True when ``hmc.sample_nuts_device`` can run this target (``sgp_small_nuts_composite``: at most 17 sampled parameters;
+        see ``targets.device_sampler_ok``)."""
+        return self.ndim <= 18 and device_sampler_ok(self.bound, "small_nuts", self.Z.shape[0], False, n_draws_total, max_treedepth)
 
-    def device_sampler_args(self):
-        return {"composite": self.device_description()}
+    def run_on_device(self, q0, tune, n_samples, rng_state, **sampler_opts):
+        b = self.bound
+        return b.engine.small_nuts(b.X, b.y, self.Z, q0, tune, n_samples, rng_state, jitter=b.jitter, kernel=b.kernel,
+                                   composite=self.device_description(), **sampler_opts)
 
     def logp_and_grad(self, theta):
-        th = [float(v) for v in theta]
-        if not all(math.isfinite(v) and abs(v) < 300.0 for v in th):
-            return -math.inf, [0.0] * self.ndim
+        th = as_floats(theta)
+        bad = (-math.inf, [0.0] * self.ndim)
+        if not in_range(th):
+            return bad
         b = self.bound
-        if hasattr(b, "_small_ok") and b._small_ok(self.Z.shape[0]):
-            # ONE launch: exp transforms, priors and the chain rule run on the device (sgp_small_eval_composite, SGP_SMALL_HMC)
-            if not all(abs(v) < 150.0 for v in th):
-                return -math.inf, [0.0] * self.ndim
-            h, info, _ = b._small_eval(self.Z, th, 1, True, False, self.device_description())
-            b.n_evals += 1
-            b.n_grads += 1
-            lp = float(h[0])
-            if info != 0 or not math.isfinite(lp):
-                return -math.inf, [0.0] * self.ndim
-            return lp, h[1:1 + self.ndim].tolist()
+        if single_launch_ok(b, self.Z.shape[0]):
+            if not all(abs(v) < 150.0 for v in th):  # (the launch's own exp range)
+                return bad
+            r = single_launch_eval(b, self.Z, th, self.ndim, composite=self.device_description())
+            return bad if r is None else r[:2]
         vals = [math.exp(v) for v in th[:-1]]
         sigma = math.exp(th[-1])
         kern = self.kernel.with_values(vals)
         F, g = self.bound.value_and_grad(self.Z, kern.block(), 1.0, sigma * sigma, raise_on_fail=False)
         if not math.isfinite(F):
-            return -math.inf, [0.0] * self.ndim
+            return bad
         gb = g["ls"]
         lp, grad = F, []
         for (name, slot, role), v, t, sd in zip(self.params, vals, th[:-1], self.sd):
@@ -303,19 +299,15 @@ class CompositeBayesianSparseGPR_HMC(torch.nn.Module):  # noqa: N801  (after the
 
     def sample_optimal_variational_hyper_dist(self, n_samples, Z_opt, tune, sampler_params=None):
         """NUTS over the log-parameters with Z fixed (reference :99-160).  Starts at the current parameter values."""
-        from .hmc import sample_nuts, sample_nuts_device
         Z = torch.as_tensor(np.asarray(Z_opt), dtype=torch.float64)
         target = CompositeHmcTarget(self.bound, Z, self.current_kernel(), self.log_prior_sd)
         start = [math.log(float(v)) for v in self.values().detach().tolist()] + [0.5 * math.log(float(self.noise().detach()))]
         scale = 0.25 if not sampler_params else sampler_params.get("step_scale", 0.25)
-        seed = None if self._seed is None else self._seed + self._n_hmc_calls
-        self._n_hmc_calls += 1
         fn = sample_nuts_device if (self.device_sampler and target.device_sampler_ok(n_samples + tune)) else sample_nuts
-        return fn(target, n_samples, tune, seed=seed, start=start, step_scale=scale)
+        return fn(target, n_samples, tune, seed=next_seed(self), start=start, step_scale=scale)
 
     def train_model(self, optimizer, max_steps=10000, hmc_scheduler=(200, 500, 1000, 1500), verbose=False,
                     num_tune_long=200, num_samples_long=50, num_tune_short=25, num_samples_short=10):
-        from .core import few_host_threads
         return few_host_threads(self._train_model)(optimizer, max_steps, list(hmc_scheduler), verbose, num_tune_long,
                                                     num_samples_long, num_tune_short, num_samples_short)
 
@@ -354,7 +346,7 @@ class CompositeBayesianSparseGPR_HMC(torch.nn.Module):  # noqa: N801  (after the
     def train_fixed_model(self, num_tune=500, num_samples=100):
         """NUTS over the hyper-parameters with Z fixed at its current value (reference :257-277)."""
         trace = self.sample_optimal_variational_hyper_dist(num_samples, self.inducing_points.detach().cpu().numpy(), num_tune)
-        return trace, [trace.get_sampler_stats('step_size')[0]], [trace.get_sampler_stats('perf_counter_diff').sum()]
+        return trace_summary(trace)
 
     # ------------------------------------------------------------------ predictive
     def posterior_predictive(self, test_x, full_cov=False):

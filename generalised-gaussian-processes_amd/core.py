@@ -16,8 +16,6 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
-
 import torch
 
 try:  # torch.distributed is plumbing; single-process use never touches it
@@ -783,267 +781,3 @@ def shard_rows(N: int, rank: int, world: int):
     lo = rank * base + min(rank, rem)
     hi = lo + base + (1 if rank < rem else 0)
     return lo, hi
-
-
-# ---------------------------------------------------------------------------------------------
-# HMC target: VFE logp + priors + log-Jacobians  (reference models/bayesian_sgpr_hmc.py:60-71)
-# ---------------------------------------------------------------------------------------------
-class HmcTarget:
-    """logp(theta_unc) and its gradient, theta_unc = [log ls_1..d, log sig_f, log sig_n].
-
-    ls ~ Gamma(alpha=2, beta=1), sig_f ~ HalfCauchy(1), sig_n ~ HalfCauchy(1), all log-transformed
-    as PyMC3 does for positive variables; covariance sig_f**2 * ExpQuad(ls), noise sig_n, Kuu jitter
-    1e-6 (``stabilize``).  A failed Cholesky gives logp = -inf (PyMC3: ``on_error='nan'``), which the
-    sampler treats as a divergence, never an exception.
-    """
-
-    def __init__(self, bound: CollapsedBound, Z, gradient="parity"):
-        """gradient: "parity" (default) -- every gradient holds 1e-6 against the CPU path (north_star): where the streaming order's error
-        estimate is beyond 3 x its tolerance a leapfrog runs in the whitened order (74 instead of 49 ms at C5).
-        "sampler" -- opt-in for NUTS in such a region: the extended order serves value AND gradient as far as its VALUE holds (2^14 x the
-        tolerance; 55 ms per leapfrog at C5).  The energy still meets 1e-8 per datum; the force is the extended order's explicit-Phibar
-        gradient, off by up to ~1e-4 relative at the far end of that range (profiles/r04_extended_order_c5.jsonl) -- but a deterministic
-        function of theta: the tier of every evaluation is the one its OWN error estimate names (`strict`), never the guard's memory of
-        earlier evaluations.  Leapfrog with a deterministic approximate force is still volume preserving and reversible, and the
-        accept step uses the accurate energy, so the chain still targets the exact posterior (tests/test_posterior_pin.py holds the
-        mode to the same 4 MCSE pin as the default); only the acceptance rate pays for the force error."""
-        if gradient not in ("parity", "sampler"):
-            raise ValueError("gradient must be 'parity' or 'sampler'")
-        self.bound = bound
-        self.Z = bound._prep_Z(Z)
-        self.d = bound.d
-        self.ndim = self.d + 2
-        self.gradient = gradient
-
-    def start(self):
-        """PyMC3's test point in the unconstrained space: Gamma(2,1) -> mean 2, HalfCauchy(1) -> 1."""
-        return [math.log(2.0)] * self.d + [0.0, 0.0]
-
-    def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
-        """True when ``hmc.sample_nuts_device`` can run this target: the bound takes the single-launch path -- and, when the run
-        length is given, its worst case (every tree at the depth limit) stays inside the persistent kernel's cumulative int
-        counters (``device_run_fits``); the host-driven sampler over the same single launch takes the longer runs."""
-        ok = hasattr(self.bound.engine, "small_nuts") and self.bound._small_ok(self.Z.shape[0])
-        return ok and (n_draws_total is None or device_run_fits(int(self.bound.X.shape[0]), n_draws_total, max_treedepth))
-
-    @staticmethod
-    def _prior(ls, sf, sn):
-        lp = sum(math.log(v) - v for v in ls)
-        g_ls = [1.0 / v - 1.0 for v in ls]
-        c = math.log(2.0) - math.log(math.pi)
-        lp += (c - math.log1p(sf * sf)) + (c - math.log1p(sn * sn))
-        return lp, g_ls, -2.0 * sf / (1.0 + sf * sf), -2.0 * sn / (1.0 + sn * sn)
-
-    @staticmethod
-    def _in_range(theta):
-        # exp() of the log-transformed variables must stay representable; beyond it the density is treated as
-        # zero (PyMC3: non-finite logp -> divergence), never an exception
-        return all(math.isfinite(float(v)) and abs(float(v)) < 300.0 for v in theta)
-
-    def constrain(self, theta):
-        th = [float(v) for v in theta]
-        return {"ls": [math.exp(v) for v in th[: self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1])}
-
-    def logp(self, theta):
-        if not self._in_range(theta):
-            return -math.inf
-        if self.bound._small_ok(self.Z.shape[0]):
-            return self.logp_and_grad(theta)[0]
-        p = self.constrain(theta)
-        F, parts = self.bound.value(self.Z, p["ls"], p["sig_f"] ** 2, p["sig_n"] ** 2, raise_on_fail=False,
-                                    **({"strict": True} if self.gradient == "sampler" else {}))
-        if parts.get("info", 0) != 0 or not math.isfinite(F):
-            return -math.inf
-        lp, _, _, _ = self._prior(p["ls"], p["sig_f"], p["sig_n"])
-        return F + lp + sum(float(v) for v in theta)
-
-    def logp_and_grad(self, theta):
-        """Returns (logp, grad list[d+2]).  One call = one HMC leapfrog's worth of device work."""
-        theta = theta.tolist() if hasattr(theta, "tolist") else [float(v) for v in theta]  # plain floats once (the sampler hands an ndarray)
-        if not self._in_range(theta):
-            return -math.inf, [0.0] * self.ndim
-        b = self.bound
-        if b._small_ok(self.Z.shape[0]):
-            # ONE launch: transforms, priors and Jacobians are applied on the device (mode SGP_SMALL_HMC)
-            h, info, _ = b._small_eval(self.Z, [float(v) for v in theta], 1, True, False)
-            b.n_evals += 1
-            b.n_grads += 1
-            hl = h.tolist()
-            lp = hl[0]
-            if info != 0 or not math.isfinite(lp):
-                return -math.inf, [0.0] * self.ndim
-            return lp, hl[1:1 + self.ndim]
-        p = self.constrain(theta)
-        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
-        kw = {"grad_reach": self.bound.extended_range, "strict": True} if self.gradient == "sampler" else {}
-        F, g = self.bound.value_and_grad(self.Z, ls, sf * sf, sn * sn, want_gz=False, raise_on_fail=False, **kw)
-        if g.get("info", 0) != 0 or not math.isfinite(F):
-            return -math.inf, [0.0] * self.ndim
-        lp, pg_ls, pg_sf, pg_sn = self._prior(ls, sf, sn)
-        gl = g["ls"].tolist()  # (one conversion: indexing a tensor element by element costs ~1.5 us each -- 27 us per leapfrog at d = 18)
-        grad = []
-        for j in range(self.d):  # d/d log ls = ls * d/d ls ; + Jacobian term 1
-            grad.append(ls[j] * (gl[j] + pg_ls[j]) + 1.0)
-        grad.append(sf * (2.0 * sf * g["sf2"] + pg_sf) + 1.0)
-        grad.append(sn * (2.0 * sn * g["s2"] + pg_sn) + 1.0)
-        return F + lp + sum(float(v) for v in theta), grad
-
-
-# ---------------------------------------------------------------------------------------------
-# exact-GP HMC target  (reference models/gpr_hmc.py:43-59)
-# ---------------------------------------------------------------------------------------------
-EXACT_MAX_N = 4096  # SGP_MAX_INDUCING: the largest N sgp_exact_eval factors
-
-
-class ExactHmcTarget:
-    """logp(theta_unc) and its gradient for NUTS over the EXACT GP marginal likelihood, theta_unc = [log ls_1..d, log sig_f, log sig_n].
-
-    ``pm.gp.Marginal(cov_func=sig_f**2 * ExpQuad(ls)).marginal_likelihood(y, X, noise=sig_n)`` with ls ~ Gamma(2, 1), sig_f ~
-    HalfCauchy(1), sig_n ~ HalfCauchy(1), log-transformed: the density is log N(y | 0, K + (sig_n^2 + jitter) I) plus
-    ``HmcTarget``'s priors and log-Jacobians.  ``jitter`` defaults to 0: Marginal adds only WhiteNoise(sig_n) to the diagonal.
-    One ``logp_and_grad`` is one ``engine.exact_eval`` (include/sgp.h: sgp_exact_eval) and one device-to-host copy.  A non-zero
-    status word (A numerically not positive definite, the conditioning gate) or a non-finite F gives (-inf, zeros), which the
-    sampler treats as a divergence; it never raises.  Single process: the target makes no collectives (N <= 4096 fits one device)."""
-
-    def __init__(self, X, y, kernel="rbf", engine=None, jitter=0.0):
-        if engine is None:
-            from .engine import HipEngine
-            engine = HipEngine(X.device if X.is_cuda else None)
-        if kernel not in ("rbf", "matern32", "matern52"):
-            raise ValueError("ExactHmcTarget takes 'rbf', 'matern32' or 'matern52' (got %r)" % (kernel,))
-        self.engine = engine
-        if X.dim() == 1:
-            X = X[:, None]
-        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
-        self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
-        if self.X.shape[0] != self.y.shape[0]:
-            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
-        if self.X.shape[0] > EXACT_MAX_N:
-            raise ValueError("the exact GP takes at most N = %d training rows (got %d)" % (EXACT_MAX_N, self.X.shape[0]))
-        self.kernel = kernel
-        self.jitter = float(jitter)
-        self.d = int(self.X.shape[1])
-        self.ndim = self.d + 2
-        self.n_evals = 0
-
-    def start(self):
-        """PyMC3's test point in the unconstrained space (``HmcTarget.start``)."""
-        return [math.log(2.0)] * self.d + [0.0, 0.0]
-
-    def constrain(self, theta):
-        th = [float(v) for v in theta]
-        return {"ls": [math.exp(v) for v in th[: self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1])}
-
-    def _eval(self, theta, want_grad):
-        p = self.constrain(theta)
-        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
-        self.n_evals += 1
-        return p, self.engine.exact_eval(self.X, self.y, ls, sf * sf, sn * sn + self.jitter, kernel=self.kernel, want_grad=want_grad)
-
-    def logp(self, theta):
-        theta = theta.tolist() if hasattr(theta, "tolist") else [float(v) for v in theta]
-        if not HmcTarget._in_range(theta):
-            return -math.inf
-        p, r = self._eval(theta, False)
-        if r["info"] != 0 or not math.isfinite(r["F"]):
-            return -math.inf
-        lp = HmcTarget._prior(p["ls"], p["sig_f"], p["sig_n"])[0]
-        return r["F"] + lp + sum(theta)
-
-    def logp_and_grad(self, theta):
-        """Returns (logp, grad list[d+2])."""
-        theta = theta.tolist() if hasattr(theta, "tolist") else [float(v) for v in theta]
-        bad = (-math.inf, [0.0] * self.ndim)
-        if not HmcTarget._in_range(theta):
-            return bad
-        p, r = self._eval(theta, True)
-        if r["info"] != 0 or not math.isfinite(r["F"]):
-            return bad
-        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
-        lp, pg_ls, pg_sf, pg_sn = HmcTarget._prior(ls, sf, sn)
-        gl = r["ls"]
-        grad = [ls[j] * (gl[j] + pg_ls[j]) + 1.0 for j in range(self.d)]  # d/d log ls = ls d/d ls ; + Jacobian 1
-        grad.append(sf * (2.0 * sf * r["sf2"] + pg_sf) + 1.0)
-        grad.append(sn * (2.0 * sn * r["s2"] + pg_sn) + 1.0)
-        if not all(math.isfinite(v) for v in grad):
-            return bad
-        return r["F"] + lp + sum(theta), grad
-
-
-# ---------------------------------------------------------------------------------------------
-# joint HMC target: theta AND the inducing inputs  (reference models/all_in_HMC.py:45-61)
-# ---------------------------------------------------------------------------------------------
-_HALF_LOG_2PI = 0.9189385332046727
-
-
-class JointHmcTarget:
-    """logp(q) and its gradient for NUTS over the hyper-parameters and the inducing inputs together,
-    q = [log ls_1..d, log sig_f, log sig_n, vec(Z)] with Z row-major M x d, untransformed (ndim = d + 2 + M d).
-
-    The same VFE ``MarginalSparse`` density and theta priors / Jacobians as ``HmcTarget``, plus Z ~ Normal(0, 1)
-    elementwise with its normalising constants, so ``logp`` is PyMC3's model logp.  Kuu jitter 1e-6 (``stabilize``).
-    A value of theta outside the representable range or a failed factorisation gives -inf, never an exception."""
-
-    def __init__(self, bound: CollapsedBound, M: int):
-        if bound.kernel == "composite":
-            raise ValueError("the joint target takes stationary kernels (no dF/dZ for composite kernels)")
-        self.bound = bound
-        self.d = bound.d
-        self.M = int(M)
-        self.ndim = self.d + 2 + self.M * self.d
-
-    def start(self):
-        """PyMC3's test point: HmcTarget's for theta, the prior mean 0 for Z."""
-        return [math.log(2.0)] * self.d + [0.0, 0.0] + [0.0] * (self.M * self.d)
-
-    def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
-        """True when ``hmc.sample_nuts_device`` can run this target (``sgp_small_nuts_joint``): the single-launch class with dF/dZ,
-        one rank, and -- when the run length is given -- a worst case inside the persistent kernel's counters."""
-        b = self.bound
-        ok = hasattr(b.engine, "small_nuts_joint") and b._small_ok(self.M, want_gz=True)
-        return ok and (n_draws_total is None or device_run_fits(int(b.X.shape[0]), n_draws_total, max_treedepth))
-
-    def _split(self, q):
-        q = q.tolist() if hasattr(q, "tolist") else [float(v) for v in q]
-        return q[:self.d + 2], q[self.d + 2:]
-
-    def constrain(self, q):
-        th, z = self._split(q)
-        return {"ls": [math.exp(v) for v in th[:self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1]),
-                "Z": np.asarray(z, dtype=np.float64).reshape(self.M, self.d)}
-
-    def logp(self, q):
-        return self.logp_and_grad(q)[0]
-
-    def logp_and_grad(self, q):
-        """Returns (logp, grad list[ndim]).  One call = one leapfrog's evaluation, dF/dZ included."""
-        th, z = self._split(q)
-        bad = (-math.inf, [0.0] * self.ndim)
-        if not HmcTarget._in_range(th) or not all(math.isfinite(v) for v in z):
-            return bad
-        b = self.bound
-        zz = np.asarray(z, dtype=np.float64)
-        Zt = torch.from_numpy(zz.reshape(self.M, self.d)).to(b.engine.device)
-        zprior = -0.5 * float(zz @ zz) - _HALF_LOG_2PI * zz.size
-        if b._small_ok(self.M, want_gz=True):
-            # ONE launch: priors and Jacobians of theta on the device (mode SGP_SMALL_HMC), dF/dZ beside them
-            h, info, gz = b._small_eval(Zt, th, 1, True, True)
-            b.n_evals += 1
-            b.n_grads += 1
-            hl = h.tolist()
-            if info != 0 or not math.isfinite(hl[0]):
-                return bad
-            gzl = (gz.detach().to("cpu").numpy().reshape(-1) - zz).tolist()
-            return hl[0] + zprior, hl[1:self.d + 3] + gzl
-        p = self.constrain(q)
-        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
-        F, g = b.value_and_grad(Zt, ls, sf * sf, sn * sn, want_gz=True, raise_on_fail=False)
-        if g.get("info", 0) != 0 or not math.isfinite(F):
-            return bad
-        lp, pg_ls, pg_sf, pg_sn = HmcTarget._prior(ls, sf, sn)
-        gl = g["ls"].tolist()
-        grad = [ls[j] * (gl[j] + pg_ls[j]) + 1.0 for j in range(self.d)]
-        grad.append(sf * (2.0 * sf * g["sf2"] + pg_sf) + 1.0)
-        grad.append(sn * (2.0 * sn * g["s2"] + pg_sn) + 1.0)
-        gz = g["Z"].detach().to("cpu").numpy().reshape(-1) - zz
-        return F + lp + sum(th) + zprior, grad + gz.tolist()

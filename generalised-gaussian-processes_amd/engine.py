@@ -571,6 +571,26 @@ class HipEngine:
         _lib.check("sgp_small_eval_batch", st)
         return outs, gz, infos
 
+    def _nuts_buffers(self, n_draws, nd, n_counters):
+        """(samples, stats, counters, info) device buffers of one persistent sampler launch."""
+        cols = int(self.lib.sgp_small_nuts_stat_cols())
+        return (self.empty(n_draws, nd), torch.zeros(n_draws * cols, dtype=torch.float64, device=self.device),
+                torch.zeros(n_counters, dtype=torch.int64, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _nuts_result(self, samples, stats, counters, info):
+        """The launch's buffers as host tensors / ints (synchronises); counters 2 and 3, where the launch has them, are the
+        joint sampler's device times in units of 1e-8 s."""
+        n_draws, cols = samples.shape[0], int(self.lib.sgp_small_nuts_stat_cols())
+        h = stats.to("cpu")
+        c = counters.to("cpu")
+        res = {"samples": samples.to("cpu"), "stats": h[: n_draws * (cols - 1)].reshape(n_draws, cols - 1),
+               "seconds": h[n_draws * (cols - 1):], "evaluations": int(c[0]), "draws": int(c[1]), "info": int(info.to("cpu")[0])}
+        if c.numel() == 4:
+            res.update(sampler_seconds=int(c[2]) * 1e-8, eval_seconds=int(c[3]) * 1e-8)
+        if res["info"] < 0:
+            self.small_reset()
+        return res
+
     def small_nuts(self, X, y, Z, q0, n_tune, n_draws, seed, jitter=1e-6, kernel="rbf", max_treedepth=10, step_scale=0.25,
                    target_accept=0.8, composite=None):
         """The whole NUTS run in one persistent launch (sgp_small_nuts / sgp_small_nuts_composite).  Returns dict(samples
@@ -589,12 +609,8 @@ class HipEngine:
         if q0d.numel() != nd:
             raise ValueError("q0 has %d entries, expected %d" % (q0d.numel(), nd))
         ws = self._small_ws(N, M, d)
-        cols = int(self.lib.sgp_small_nuts_stat_cols())
-        samples = self.empty(n_draws, nd)
-        stats = torch.zeros(n_draws * cols, dtype=torch.float64, device=self.device)
-        counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+        samples, stats, counters, info = self._nuts_buffers(n_draws, nd, 2)
         theta, out = self.empty(nd), self.empty(nout)
-        info = torch.zeros(1, dtype=torch.int32, device=self.device)
         head = (self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._ptr(q0d))
         tail = (float(jitter), int(n_tune), int(n_draws), int(max_treedepth), float(step_scale), float(target_accept),
                 int(seed) & ((1 << 64) - 1), self._ptr(theta), self._ptr(samples), self._ptr(stats),
@@ -605,13 +621,7 @@ class HipEngine:
             _lib.check("sgp_small_nuts_composite", self._cf.sgp_small_nuts_composite(*head, *cargs, N, M, d, *tail))
         else:
             _lib.check("sgp_small_nuts", self._cf.sgp_small_nuts(*head, N, M, d, _kernel_id(kernel), *tail))
-        h = stats.to("cpu")
-        c = counters.to("cpu")
-        res = {"samples": samples.to("cpu"), "stats": h[: n_draws * (cols - 1)].reshape(n_draws, cols - 1),
-               "seconds": h[n_draws * (cols - 1):], "evaluations": int(c[0]), "draws": int(c[1]), "info": int(info.to("cpu")[0])}
-        if res["info"] < 0:
-            self.small_reset()
-        return res
+        return self._nuts_result(samples, stats, counters, info)
 
     def small_nuts_joint(self, X, y, M, q0, n_tune, n_draws, seed, jitter=1e-6, kernel="rbf", max_treedepth=10, step_scale=0.25,
                          target_accept=0.8):
@@ -632,25 +642,14 @@ class HipEngine:
         if nbytes == 0:
             raise ValueError("shape N=%d M=%d d=%d is outside the single-launch path" % (N, M, d))
         small = self._small_ws(N, M, d, nbytes)  # the per-stream single-launch workspace, sized to hold the sampler's vectors too
-        cols = int(self.lib.sgp_small_nuts_stat_cols())
-        samples = self.empty(n_draws, nd)
-        stats = torch.zeros(n_draws * cols, dtype=torch.float64, device=self.device)
-        counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        samples, stats, counters, info = self._nuts_buffers(n_draws, nd, 4)
         out = self.empty(d + 5)
-        info = torch.zeros(1, dtype=torch.int32, device=self.device)
         _lib.check("sgp_small_nuts_joint", self._cf.sgp_small_nuts_joint(
             self._ptr(X), d, self._ptr(y), self._ptr(q0d), N, M, d, _kernel_id(kernel), float(jitter), int(n_tune), int(n_draws),
             int(max_treedepth), float(step_scale), float(target_accept), int(seed) & ((1 << 64) - 1), self._ptr(samples),
             self._ptr(stats), C.c_void_p(counters.data_ptr()), self._ptr(out), C.c_void_p(info.data_ptr()), self._ptr(small),
             small.numel(), self._stream()))
-        h = stats.to("cpu")
-        c = counters.to("cpu")
-        res = {"samples": samples.to("cpu"), "stats": h[: n_draws * (cols - 1)].reshape(n_draws, cols - 1),
-               "seconds": h[n_draws * (cols - 1):], "evaluations": int(c[0]), "draws": int(c[1]), "info": int(info.to("cpu")[0]),
-               "sampler_seconds": int(c[2]) * 1e-8, "eval_seconds": int(c[3]) * 1e-8}
-        if res["info"] < 0:
-            self.small_reset()
-        return res
+        return self._nuts_result(samples, stats, counters, info)
 
     def small_result(self, d: int):
         """[out (d + 5) | status word] in one buffer, so one device-to-host copy ends an evaluation."""

@@ -19,6 +19,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .core import SgpTimeoutError, device_run_fits, few_host_threads  # (core imports nothing from this module)
+
 
 # ---------------------------------------------------------------------------------------------
 # random numbers shared with the device sampler
@@ -353,48 +355,64 @@ def _trace_row(c, q):
     return row
 
 
+def next_seed(model) -> Optional[int]:
+    """The seed of a model's next sampler run: its own seed plus the number of runs so far (None stays None)."""
+    n = model._n_hmc_calls
+    model._n_hmc_calls += 1
+    return None if model._seed is None else model._seed + n
+
+
+def trace_summary(trace):
+    """What the reference's ``train_model`` / ``train_fixed_model`` return: (trace, [step size], [summed sampling seconds])."""
+    return trace, [trace.get_sampler_stats('step_size')[0]], [trace.get_sampler_stats('perf_counter_diff').sum()]
+
+
+def _find_start(target, evaluate, rng, start):
+    """The chain's first position and ``evaluate``'s result there (``evaluate(q)[0]`` is logp).  ``start=None``: PyMC3's test
+    point (Gamma(2,1) -> mean 2 ; HalfCauchy(1) -> 1, in log space, for a target without ``start()``) plus U(-1, 1) jitter,
+    redrawn up to 20 times while the density there is zero; a user-supplied start is never replaced."""
+    nd = target.ndim
+
+    def test_point():
+        base = target.start() if hasattr(target, "start") else [math.log(2.0)] * (nd - 2) + [0.0, 0.0]
+        return np.asarray(base, dtype=np.float64) + rng.uniform(-1.0, 1.0, nd)
+
+    q = test_point() if start is None else np.asarray(start, dtype=np.float64).copy()
+    r = evaluate(q)
+    tries = 0
+    while start is None and not math.isfinite(r[0]) and tries < 20:
+        q = test_point()
+        r = evaluate(q)
+        tries += 1
+    if not math.isfinite(r[0]):
+        raise RuntimeError("could not find a starting point with finite log-density" if start is None
+                           else "the log-density is not finite at the supplied start")
+    return q, r
+
+
 def sample_nuts_device(target, n_samples: int, tune: int, seed: Optional[int] = None, start: Optional[Sequence[float]] = None,
                        step_scale=0.25, target_accept=0.8, max_treedepth=10) -> Trace:
     """``pm.sample(n_samples, tune=tune, chains=1)`` entirely on the GPU: one persistent launch (``sgp_small_nuts``) runs the
     sampler and every leapfrog's evaluation; theta, the momentum and the sampler state never visit the host (SURVEY section 8
-    f-1).  ``target`` is an ``HmcTarget``, ``CompositeHmcTarget`` or ``JointHmcTarget`` (``sgp_small_nuts_joint``) whose bound takes the single-launch path (M <= 128, one rank).  Same algorithm and
+    f-1).  ``target`` is an ``HmcTarget``, ``CompositeHmcTarget`` or ``JointHmcTarget``: it launches itself
+    (``target.run_on_device``) and its bound takes the single-launch path (M <= 128, one rank).  Same algorithm and
     random stream as ``NUTS(..., rng=SplitMix(seed))``; the trace has the surface the reference reads
     (``trace['ls']``, ``trace[i]``, ``get_sampler_stats('step_size' | 'perf_counter_diff')``)."""
     b = target.bound
     if not target.device_sampler_ok():
         raise ValueError("the device sampler needs the single-launch path (M <= 128, one rank; stationary kernels d <= 24, "
                          "composite kernels d <= 8)")
-    from .core import device_run_fits
     if not device_run_fits(int(b.X.shape[0]), n_samples + tune, max_treedepth):
         raise ValueError("a run of %d draws at tree depth %d could overflow the persistent kernel's counters: use sample_nuts "
                          "(host-driven, same single-launch evaluations) or a smaller max_treedepth" % (n_samples + tune, max_treedepth))
-    nd = target.ndim
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0] >> 1)
     rng = SplitMix(seed)
-    if start is None:  # PyMC3's jitter around the test point; redrawn while the density there is zero
-        q = np.asarray(target.start(), dtype=np.float64) + rng.uniform(-1.0, 1.0, nd)
-        tries = 0
-        while not math.isfinite(target.logp(q)) and tries < 20:
-            q = np.asarray(target.start(), dtype=np.float64) + rng.uniform(-1.0, 1.0, nd)
-            tries += 1
-    else:
-        q = np.asarray(start, dtype=np.float64).copy()
-    if not math.isfinite(target.logp(q)):
-        raise RuntimeError("could not find a starting point with finite log-density" if start is None
-                           else "the log-density is not finite at the supplied start")
+    q, _ = _find_start(target, lambda q: (target.logp(q),), rng, start)
     t0 = time.perf_counter()
-    from .core import JointHmcTarget
-    if isinstance(target, JointHmcTarget):  # Z is part of the position
-        r = b.engine.small_nuts_joint(b.X, b.y, target.M, q, tune, n_samples, rng.s, jitter=b.jitter, kernel=b.kernel,
-                                      max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept)
-    else:
-        extra = target.device_sampler_args() if hasattr(target, "device_sampler_args") else {}  # composite kernels: the structure
-        r = b.engine.small_nuts(b.X, b.y, target.Z, q, tune, n_samples, rng.s, jitter=b.jitter, kernel=b.kernel,
-                                max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept, **extra)
+    r = target.run_on_device(q, tune, n_samples, rng.s, max_treedepth=max_treedepth, step_scale=step_scale, target_accept=target_accept)
     wall = time.perf_counter() - t0
     if r["info"] < 0:
-        from .core import SgpTimeoutError
         raise SgpTimeoutError()
     if r["draws"] != tune + n_samples:
         raise RuntimeError("the device sampler stopped after %d of %d draws" % (r["draws"], tune + n_samples))
@@ -414,12 +432,7 @@ def sample_nuts_device(target, n_samples: int, tune: int, seed: Optional[int] = 
     return tr
 
 
-def _few_threads(fn):
-    from .core import few_host_threads  # (core imports nothing from this module)
-    return few_host_threads(fn)
-
-
-@_few_threads
+@few_host_threads
 def sample_nuts(target, n_samples: int, tune: int, seed: Optional[int] = None, start: Optional[Sequence[float]] = None,
                 step_scale=0.25, target_accept=0.8, max_treedepth=10, progress: Optional[Callable[[int, dict], None]] = None,
                 group=None) -> Trace:
@@ -429,22 +442,7 @@ def sample_nuts(target, n_samples: int, tune: int, seed: Optional[int] = None, s
     nd = target.ndim
     seed = shared_seed(seed, group)
     nuts = NUTS(target.logp_and_grad, nd, step_scale=step_scale, target_accept=target_accept, max_treedepth=max_treedepth, seed=seed)
-
-    def test_point():
-        # PyMC3 test point (Gamma(2,1) -> mean 2 ; HalfCauchy(1) -> 1) in log space, plus U(-1,1) jitter
-        base = np.asarray(target.start(), dtype=np.float64) if hasattr(target, "start") else np.array([math.log(2.0)] * (nd - 2) + [0.0, 0.0])
-        return base + nuts.rng.uniform(-1.0, 1.0, nd)
-
-    q = test_point() if start is None else np.asarray(start, dtype=np.float64).copy()
-    lp, g = nuts._eval(q)
-    tries = 0
-    while start is None and not math.isfinite(lp) and tries < 20:  # unlucky jitter: redraw (a user-supplied start is never replaced)
-        q = test_point()
-        lp, g = nuts._eval(q)
-        tries += 1
-    if not math.isfinite(lp):
-        raise RuntimeError("could not find a starting point with finite log-density" if start is None
-                           else "the log-density is not finite at the supplied start")
+    q, (lp, g) = _find_start(target, nuts._eval, nuts.rng, start)
     nuts.mass = DiagMassAdapter(nd, initial_mean=q)  # jitter+adapt_diag: mean = start, variance 1, weight 10
     samples, stat_rows = [], []
     for it in range(tune + n_samples):

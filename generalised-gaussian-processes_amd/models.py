@@ -20,11 +20,11 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .core import (EXACT_MAX_N, CollapsedBound, ExactHmcTarget, HmcTarget, JointHmcTarget, NotPositiveDefiniteError, SgpTimeoutError,
-                   few_host_threads)
+from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, few_host_threads
 from .gp_shim import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, LazyPredictive,
                       MultivariateNormal, RBFKernel, ScaleKernel, TrainPrior, ZeroMean)
-from .hmc import Trace, sample_nuts, sample_nuts_device
+from .hmc import Trace, next_seed, sample_nuts, sample_nuts_device, trace_summary
+from .targets import EXACT_MAX_N, ExactHmcTarget, HmcTarget, JointHmcTarget
 
 FULL_COV_MAX_T = 4096  # predictive covariance is T x T; beyond this only mean / variance are formed
 
@@ -47,6 +47,7 @@ class SparseGPR(ExactGP):
         self.jitter = float(jitter)
         self._engine = engine
         self._cb: Optional[CollapsedBound] = None
+        self._hmc_cb: Optional[CollapsedBound] = None
         dev = engine.device if engine is not None else train_x.device
         self.to(dev)
 
@@ -60,6 +61,13 @@ class SparseGPR(ExactGP):
             self._cb = CollapsedBound(self.train_x, self.train_y, kernel=self.base_covar_module.base_kernel.kernel_name,
                                       jitter=self.jitter, engine=self._engine)
         return self._cb
+
+    def _hmc_bound(self) -> CollapsedBound:
+        """The bound the NUTS targets evaluate: PyMC3's MarginalSparse always stabilises Kuu with 1e-6 I (reference
+        models/bayesian_sgpr_hmc.py:66), whatever ``jitter`` the optimisation uses."""
+        if self._hmc_cb is None:
+            self._hmc_cb = CollapsedBound(self.train_x, self.train_y, kernel="rbf", jitter=1e-6, engine=self._bound().engine)
+        return self._hmc_cb
 
     def _hypers(self):
         ls = self.base_covar_module.base_kernel.lengthscale.detach().reshape(-1).tolist()
@@ -154,11 +162,10 @@ class BayesianSparseGPR_HMC(SparseGPR):  # noqa: N801  (reference class name)
     def __init__(self, train_x, train_y, likelihood, Z_init, engine=None, jitter: float = 0.0, seed: Optional[int] = None):
         super().__init__(train_x, train_y, likelihood, Z_init, engine=engine, jitter=jitter)
         self.data_dim = self.train_x.shape[1]
-        self._hmc_cb: Optional[CollapsedBound] = None
         self._seed = seed
         self._n_hmc_calls = 0
         self.device_sampler = True  # NUTS on the device when the problem takes the single-launch path (M <= 128)
-        self.hmc_gradient = "parity"  # or "sampler": see core.HmcTarget (large shards in the streaming-order guard's regime)
+        self.hmc_gradient = "parity"  # or "sampler": see targets.HmcTarget (large shards in the streaming-order guard's regime)
         self.batched_theta_loss = True  # ... and the theta-averaged loss of the alternating schedule in one launch
 
     def freeze_kernel_hyperparameters(self):
@@ -166,28 +173,17 @@ class BayesianSparseGPR_HMC(SparseGPR):  # noqa: N801  (reference class name)
             if name != 'covar_module.inducing_points':
                 parameter.requires_grad = False
 
-    def _hmc_bound(self):
-        # PyMC3's MarginalSparse always stabilises Kuu with 1e-6 I (reference models/bayesian_sgpr_hmc.py:66)
-        if self._hmc_cb is None:
-            self._hmc_cb = CollapsedBound(self.train_x, self.train_y, kernel="rbf", jitter=1e-6, engine=self._bound().engine)
-        return self._hmc_cb
-
     def sample_optimal_variational_hyper_dist(self, n_samples, input_dim, Z_opt, tune, sampler_params=None) -> Trace:
         """NUTS over (ls, sig_f, sig_n) with Z fixed at Z_opt (reference models/bayesian_sgpr_hmc.py:58-80)."""
         Z = torch.as_tensor(np.asarray(Z_opt), dtype=torch.float64)
         target = HmcTarget(self._hmc_bound(), Z, gradient=self.hmc_gradient)
         scale = 0.25 if not sampler_params else sampler_params.get('step_scale', 0.25)
-        seed = None if self._seed is None else self._seed + self._n_hmc_calls
-        self._n_hmc_calls += 1
-        if self.device_sampler and target.device_sampler_ok(n_samples + tune):
-            # the whole of pm.sample() in one persistent launch: theta, momentum and the tree never leave the GPU
-            return sample_nuts_device(target, n_samples, tune, seed=seed, step_scale=scale)
-        return sample_nuts(target, n_samples, tune, seed=seed, step_scale=scale)
+        # on the device: the whole of pm.sample() in one persistent launch, theta, momentum and the tree never leave the GPU
+        fn = sample_nuts_device if self.device_sampler and target.device_sampler_ok(n_samples + tune) else sample_nuts
+        return fn(target, n_samples, tune, seed=next_seed(self), step_scale=scale)
 
     def update_model_to_hyper(self, elbo, hyper_sample):
-        elbo.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
-        elbo.model.base_covar_module.outputscale = hyper_sample['sig_f'] ** 2
-        elbo.model.base_covar_module.base_kernel.lengthscale = hyper_sample['ls']
+        _bind_draw(elbo.likelihood, elbo.model.base_covar_module, hyper_sample)
 
     @few_host_threads
     def train_model(self, optimizer, max_steps=10000, hmc_scheduler=(200, 500, 1000, 1500), verbose=True,
@@ -250,40 +246,85 @@ class BayesianSparseGPR_HMC(SparseGPR):  # noqa: N801  (reference class name)
         self.train()
         self.likelihood.train()
         Z_opt = self.inducing_points.detach().cpu().numpy()
-        trace_hyper = self.sample_optimal_variational_hyper_dist(num_samples, self.data_dim, Z_opt, num_tune, None)
-        return (trace_hyper, [trace_hyper.get_sampler_stats('step_size')[0]],
-                [trace_hyper.get_sampler_stats('perf_counter_diff').sum()])
+        return trace_summary(self.sample_optimal_variational_hyper_dist(num_samples, self.data_dim, Z_opt, num_tune, None))
 
 
-def _mixture_batched(model, test_x, trace_hyper):
-    """The same list of predictives from sgp_mixture_predict: eight theta samples per chain of launches, the PSD gate
-    cholesky(cov + 1e-4 I) of all of them in one dataflow launch, ONE status copy for the whole trace.
-    Returns None when the batched call does not apply (test double, several ranks, composite kernels, T beyond the full-
-    covariance limit, ``model.batched_mixture = False``): the caller then runs the reference's per-sample loop."""
+def _bind_draw(likelihood, cov, draw, inducing=None):
+    """Bind one draw of a trace: the noise, ``cov``'s (a ScaleKernel) outputscale and lengthscales, and -- ``inducing``: the
+    model's inducing-point parameter -- the draw's own Z."""
+    likelihood.noise_covar.noise = draw['sig_n'] ** 2
+    cov.outputscale = draw['sig_f'] ** 2
+    cov.base_kernel.lengthscale = draw['ls']
+    if inducing is not None:
+        with torch.no_grad():
+            inducing.data = torch.as_tensor(np.asarray(draw['Z']), dtype=torch.float64).to(inducing.device).reshape(inducing.shape).clone()
+
+
+def _bind_sparse(model, draw):
+    _bind_draw(model.likelihood, model.base_covar_module, draw)
+
+
+def _bind_joint(model, draw):
+    _bind_draw(model.likelihood, model.base_covar_module, draw, model.covar_module.inducing_points)
+
+
+def _bind_exact(model, draw):
+    _bind_draw(model.likelihood, model.covar_module, draw)
+
+
+def _mixture_loop(model, test_x, trace_hyper, bind, gate_jitter):
+    """The reference's per-draw loop: bind the draw, predict, keep the predictive if cholesky(cov + gate_jitter I) succeeds (on
+    the device the T x T covariance is factored where it is and only the status word crosses PCIe), else print and skip it."""
+    preds = []
+    for i in range(len(trace_hyper)):
+        model.train()
+        model.likelihood.train()
+        bind(model, trace_hyper[i])
+        with torch.no_grad():
+            model.eval()
+            model.likelihood.eval()
+            try:
+                pred = model.likelihood(model(test_x))
+                if not pred.is_psd(gate_jitter):
+                    raise RuntimeError("predictive covariance not positive definite")
+                preds.append(pred)
+            except SgpTimeoutError:
+                raise  # a device scheduling fault is never a numerical outcome: it must not thin the mixture silently
+            except (RuntimeError, NotPositiveDefiniteError):
+                print('Not psd for sample ' + str(i))
+    return preds
+
+
+def _mixture_batched(model, test_x, trace_hyper, bind, gate_jitter, own_Z=False):
+    """The same list of predictives from sgp_mixture_predict (``own_Z``: sgp_mixture_predict_zs, every draw with its own Z):
+    eight draws per chain of launches, the PSD gate of all of them in one dataflow launch, ONE status copy for the whole trace
+    (SURVEY section 8 f-2).  Returns None when the batched call does not apply (test double, several ranks, composite kernels, T
+    beyond the full-covariance limit): the caller then runs the per-draw loop."""
     b = model._bound()
     e = b.engine
-    if (not getattr(model, "batched_mixture", True) or not hasattr(e, "mixture_predict") or b.world != 1 or b.kernel == "composite"
-            or len(trace_hyper) == 0):
+    if not hasattr(e, "mixture_predict") or b.world != 1 or b.kernel == "composite" or len(trace_hyper) == 0:
         return None
     tx = test_x[:, None] if test_x.dim() == 1 else test_x
     if tx.shape[0] > FULL_COV_MAX_T or tx.shape[0] > 8192:
         return None
-    S = len(trace_hyper)
+    S, d = len(trace_hyper), b.d
     ls = [np.asarray(trace_hyper[i]['ls'], dtype=np.float64).reshape(-1) for i in range(S)]
-    d = b.d
     ls = [np.repeat(v, d) if v.size == 1 and d > 1 else v for v in ls]
     sf2 = [float(trace_hyper[i]['sig_f']) ** 2 for i in range(S)]
     s2 = [float(trace_hyper[i]['sig_n']) ** 2 for i in range(S)]
+    if own_Z:
+        Z = torch.from_numpy(np.stack([np.asarray(trace_hyper[i]['Z'], dtype=np.float64).reshape(-1, d) for i in range(S)])).to(e.device)
+    else:
+        Z = b._prep_Z(model.covar_module.inducing_points)
     Xs = tx.detach().to(dtype=torch.float64, device=e.device).contiguous()
     with torch.no_grad():
-        r = e.mixture_predict(b.X, b.y, Xs, b._prep_Z(model.covar_module.inducing_points), ls, sf2, s2, jitter=b.jitter, kernel=b.kernel,
-                              pred_noise=True, full_cov=True, gate_jitter=1e-4)
+        r = e.mixture_predict(b.X, b.y, Xs, Z, ls, sf2, s2, jitter=b.jitter, kernel=b.kernel, pred_noise=True, full_cov=True,
+                              gate_jitter=gate_jitter)
         status = torch.stack([r["info"], r["gate"]]).to("cpu")  # the one host round trip of the whole mixture
-    # the loop leaves the model at the last sample's hyper-parameters (models/bayesian_sgpr_hmc.py:206-208): so does this
-    last = trace_hyper[S - 1]
-    model.likelihood.noise_covar.noise = last['sig_n'] ** 2
-    model.base_covar_module.outputscale = last['sig_f'] ** 2
-    model.base_covar_module.base_kernel.lengthscale = last['ls']
+    # the loop leaves the model in eval mode at the last draw (models/bayesian_sgpr_hmc.py:206-208): so does this
+    model.train()
+    model.likelihood.train()
+    bind(model, trace_hyper[S - 1])
     model.eval()
     model.likelihood.eval()
     preds = []
@@ -300,33 +341,10 @@ def _mixture_batched(model, test_x, trace_hyper):
 
 def mixture_posterior_predictive(model, test_x, trace_hyper):
     """One predictive per theta sample; samples whose predictive covariance fails the reference's PSD gate
-    (cholesky(cov + 1e-4 I)) are skipped, never raised (reference models/bayesian_sgpr_hmc.py:198-231)."""
-    batched = _mixture_batched(model, test_x, trace_hyper)
-    if batched is not None:
-        return batched
-    preds = []
-    for i in range(len(trace_hyper)):
-        hyper_sample = trace_hyper[i]
-        model.train()
-        model.likelihood.train()
-        model.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
-        model.base_covar_module.outputscale = hyper_sample['sig_f'] ** 2
-        model.base_covar_module.base_kernel.lengthscale = hyper_sample['ls']
-        with torch.no_grad():
-            model.eval()
-            model.likelihood.eval()
-            try:
-                pred = model.likelihood(model(test_x))
-                # the reference's PSD gate, cholesky(cov + 1e-4 I): on the device the T x T covariance is factored where
-                # it is and only the status word crosses PCIe (no per-sample T x T copy)
-                if not pred.is_psd(1e-4):
-                    raise RuntimeError("predictive covariance not positive definite")
-                preds.append(pred)
-            except SgpTimeoutError:
-                raise  # a device scheduling fault is never a numerical outcome: it must not thin the mixture silently
-            except (RuntimeError, NotPositiveDefiniteError):
-                print('Not psd for sample ' + str(i))
-    return preds
+    (cholesky(cov + 1e-4 I)) are skipped, never raised (reference models/bayesian_sgpr_hmc.py:198-231).  Batched where that
+    applies (``_mixture_batched``); ``model.batched_mixture = False`` selects the loop."""
+    preds = _mixture_batched(model, test_x, trace_hyper, _bind_sparse, 1e-4) if getattr(model, "batched_mixture", True) else None
+    return preds if preds is not None else _mixture_loop(model, test_x, trace_hyper, _bind_sparse, 1e-4)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -342,81 +360,24 @@ class all_in_HMC(SparseGPR):  # noqa: N801  (reference class name)
         self.data_dim = self.train_x.shape[1]
         self._seed = seed
         self._n_hmc_calls = 0
-        self._hmc_cb: Optional[CollapsedBound] = None
         self.device_sampler = True  # the persistent joint kernel when the problem takes the single-launch path (M <= 128)
-
-    def _hmc_bound(self):
-        if self._hmc_cb is None:  # PyMC3 stabilises Kuu with 1e-6 I
-            self._hmc_cb = CollapsedBound(self.train_x, self.train_y, kernel="rbf", jitter=1e-6, engine=self._bound().engine)
-        return self._hmc_cb
 
     def sample(self, n_samples, input_dim, tune) -> Trace:
         """``pm.sample(n_samples, tune=tune, chains=1)`` over the joint model; ``trace['Z']`` has shape (n, M, d)."""
         if int(input_dim) != self.data_dim:
             raise ValueError("input_dim %d does not match the training inputs (%d)" % (input_dim, self.data_dim))
         target = JointHmcTarget(self._hmc_bound(), self.num_inducing)
-        seed = None if self._seed is None else self._seed + self._n_hmc_calls
-        self._n_hmc_calls += 1
-        if self.device_sampler and target.device_sampler_ok(n_samples + tune):
-            return sample_nuts_device(target, n_samples, tune, seed=seed)
-        return sample_nuts(target, n_samples, tune, seed=seed)
+        fn = sample_nuts_device if self.device_sampler and target.device_sampler_ok(n_samples + tune) else sample_nuts
+        return fn(target, n_samples, tune, seed=next_seed(self))
 
     def train_model(self):
         """500 tuning + 100 draws (reference models/all_in_HMC.py:63-79).  Returns (trace_hyper, [step_size], [perf_time sum])."""
         self.train()
         self.likelihood.train()
-        trace_hyper = self.sample(100, self.data_dim, 500)
-        return (trace_hyper, [trace_hyper.get_sampler_stats('step_size')[0]],
-                [trace_hyper.get_sampler_stats('perf_counter_diff').sum()])
+        return trace_summary(self.sample(100, self.data_dim, 500))
 
     def optimal_q_u(self):
         return self(self.covar_module.inducing_points)
-
-
-def _bind_sample(model, hyper_sample):
-    model.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
-    model.base_covar_module.outputscale = hyper_sample['sig_f'] ** 2
-    model.base_covar_module.base_kernel.lengthscale = hyper_sample['ls']
-    with torch.no_grad():
-        Zp = model.covar_module.inducing_points
-        Zp.data = torch.as_tensor(np.asarray(hyper_sample['Z']), dtype=torch.float64).to(Zp.device).reshape(Zp.shape).clone()
-
-
-def _full_mixture_batched(model, test_x, trace_hyper):
-    """full_mixture_posterior_predictive's predictives from sgp_mixture_predict_zs, or None where it does not apply."""
-    b = model._bound()
-    e = b.engine
-    if not hasattr(e, "mixture_predict") or b.world != 1 or b.kernel == "composite" or len(trace_hyper) == 0:
-        return None
-    tx = test_x[:, None] if test_x.dim() == 1 else test_x
-    if tx.shape[0] > FULL_COV_MAX_T or tx.shape[0] > 8192:
-        return None
-    S, d = len(trace_hyper), b.d
-    ls = [np.asarray(trace_hyper[i]['ls'], dtype=np.float64).reshape(-1) for i in range(S)]
-    ls = [np.repeat(v, d) if v.size == 1 and d > 1 else v for v in ls]
-    sf2 = [float(trace_hyper[i]['sig_f']) ** 2 for i in range(S)]
-    s2 = [float(trace_hyper[i]['sig_n']) ** 2 for i in range(S)]
-    Zs = np.stack([np.asarray(trace_hyper[i]['Z'], dtype=np.float64).reshape(-1, d) for i in range(S)])
-    Xs = tx.detach().to(dtype=torch.float64, device=e.device).contiguous()
-    with torch.no_grad():
-        r = e.mixture_predict(b.X, b.y, Xs, torch.from_numpy(Zs).to(e.device), ls, sf2, s2, jitter=b.jitter, kernel=b.kernel,
-                              pred_noise=True, full_cov=True, gate_jitter=1e-5)
-        status = torch.stack([r["info"], r["gate"]]).to("cpu")
-    model.train()
-    model.likelihood.train()
-    _bind_sample(model, trace_hyper[S - 1])
-    model.eval()
-    model.likelihood.eval()
-    preds = []
-    for i in range(S):
-        info, gate = int(status[0, i]), int(status[1, i])
-        if info < 0 or gate < 0:
-            raise SgpTimeoutError()
-        if info != 0 or gate != 0:
-            print('Not psd for sample ' + str(i))
-            continue
-        preds.append(MultivariateNormal(r["mean"][i], r["cov"][i], variance=r["var"][i], engine=e))
-    return preds
 
 
 # ---------------------------------------------------------------------------------------------
@@ -496,81 +457,29 @@ class GPR_HMC(ExactGP):  # noqa: N801  (reference class name)
         """``pm.sample(n_samples, tune=tune, chains=1)`` over the exact model; the trace has ``ls``, ``sig_f``, ``sig_n``."""
         if int(input_dim) != self.data_dim:
             raise ValueError("input_dim %d does not match the training inputs (%d)" % (input_dim, self.data_dim))
-        seed = None if self._seed is None else self._seed + self._n_hmc_calls
-        self._n_hmc_calls += 1
-        return sample_nuts(self._exact_target(), n_samples, tune, seed=seed)
+        return sample_nuts(self._exact_target(), n_samples, tune, seed=next_seed(self))
 
     def train_model(self):
         """50 tuning + 10 draws (reference models/gpr_hmc.py:63-79).  Returns (trace_hyper, [step_size], [perf_time sum])."""
         self.train()
         self.likelihood.train()
-        trace_hyper = self.sample_optimal_variational_hyper_dist(10, self.data_dim, 50)
-        return (trace_hyper, [trace_hyper.get_sampler_stats('step_size')[0]],
-                [trace_hyper.get_sampler_stats('perf_counter_diff').sum()])
-
-
-def _gpr_full_mixture(model, test_x, trace_hyper):
-    """full_mixture_posterior_predictive of reference models/gpr_hmc.py:84-119: one exact predictive per draw; sig_n^2 < 1e-4 ->
-    sig_n = 0.01 in the trace row itself; a predictive whose cholesky(cov + 1e-2 I) fails is skipped with "Not psd for sample i"."""
-    preds = []
-    for i in range(len(trace_hyper)):
-        hyper_sample = trace_hyper[i]
-        model.train()
-        model.likelihood.train()
-        if hyper_sample['sig_n'] ** 2 < 1e-4:
-            hyper_sample['sig_n'] = 0.01
-        model.likelihood.noise_covar.noise = hyper_sample['sig_n'] ** 2
-        model.covar_module.outputscale = hyper_sample['sig_f'] ** 2
-        model.covar_module.base_kernel.lengthscale = hyper_sample['ls']
-        with torch.no_grad():
-            model.eval()
-            model.likelihood.eval()
-            try:
-                pred = model.likelihood(model(test_x))
-                if not pred.is_psd(1e-2):
-                    raise RuntimeError("predictive covariance not positive definite")
-                preds.append(pred)
-            except SgpTimeoutError:
-                raise
-            except (RuntimeError, NotPositiveDefiniteError):
-                print('Not psd for sample ' + str(i))
-    return preds
+        return trace_summary(self.sample_optimal_variational_hyper_dist(10, self.data_dim, 50))
 
 
 def full_mixture_posterior_predictive(model, test_x, trace_hyper):
     """One predictive per joint draw, each with THAT draw's Z (reference models/all_in_HMC.py:84-119): a draw with
     sig_n^2 < 1e-4 gets sig_n = 0.01 (as in the reference, the trace row itself is changed); a predictive whose covariance fails
-    cholesky(cov + 1e-5 I) is skipped with "Not psd for sample i".  The model is left at the last draw, Z included.
-    Batched through sgp_mixture_predict_zs (eight draws per chain of launches, each with its own Z); the per-draw loop below is
+    cholesky(cov + 1e-5 I) is skipped and named on stdout (``_mixture_loop``).  The model is left at the last draw, Z included.
+    Batched through sgp_mixture_predict_zs (eight draws per chain of launches, each with its own Z); the per-draw loop is
     the fallback where that does not apply (test double, several ranks, T beyond the full-covariance limit).
-    For a ``GPR_HMC`` model: the exact predictive per draw (reference models/gpr_hmc.py:84-119, ``_gpr_full_mixture``)."""
-    if isinstance(model, GPR_HMC):
-        return _gpr_full_mixture(model, test_x, trace_hyper)
+    For a ``GPR_HMC`` model: the exact predictive per draw, gate cholesky(cov + 1e-2 I) (reference models/gpr_hmc.py:84-119)."""
     for i in range(len(trace_hyper)):
         if trace_hyper[i]['sig_n'] ** 2 < 1e-4:
             trace_hyper[i]['sig_n'] = 0.01
-    batched = _full_mixture_batched(model, test_x, trace_hyper)
-    if batched is not None:
-        return batched
-    preds = []
-    for i in range(len(trace_hyper)):
-        hyper_sample = trace_hyper[i]
-        model.train()
-        model.likelihood.train()
-        _bind_sample(model, hyper_sample)
-        with torch.no_grad():
-            model.eval()
-            model.likelihood.eval()
-            try:
-                pred = model.likelihood(model(test_x))
-                if not pred.is_psd(1e-5):
-                    raise RuntimeError("predictive covariance not positive definite")
-                preds.append(pred)
-            except SgpTimeoutError:
-                raise
-            except (RuntimeError, NotPositiveDefiniteError):
-                print('Not psd for sample ' + str(i))
-    return preds
+    if isinstance(model, GPR_HMC):
+        return _mixture_loop(model, test_x, trace_hyper, _bind_exact, 1e-2)
+    preds = _mixture_batched(model, test_x, trace_hyper, _bind_joint, 1e-5, own_Z=True)
+    return preds if preds is not None else _mixture_loop(model, test_x, trace_hyper, _bind_joint, 1e-5)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,0 +1,301 @@
+"""NUTS targets over ``[log ls_1..d, log sig_f, log sig_n]``: what ``hmc.sample_nuts`` / ``sample_nuts_device`` evaluate.
+
+``HmcTarget`` (VFE bound, Z fixed), ``ExactHmcTarget`` (exact marginal likelihood) and ``JointHmcTarget`` (VFE bound, Z sampled)
+share one density recipe -- PyMC3's log transform, its test point, the theta priors and the chain rule to the unconstrained
+variables -- which lives here once, beside the two pieces every target over a ``CollapsedBound`` shares (``composite.
+CompositeHmcTarget`` included): the single-launch evaluation and the test for the device-resident sampler.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from .core import CollapsedBound, device_run_fits
+
+_LOG_2_OVER_PI = math.log(2.0) - math.log(math.pi)
+_HALF_LOG_2PI = 0.9189385332046727
+
+
+# ---------------------------------------------------------------------------------------------
+# shared by every target
+# ---------------------------------------------------------------------------------------------
+def as_floats(q):
+    """The position as plain floats, converted once (the sampler hands an ndarray)."""
+    return q.tolist() if hasattr(q, "tolist") else [float(v) for v in q]
+
+
+def in_range(theta):
+    """exp() of the log-transformed variables must stay representable; beyond it the density is treated as zero (PyMC3:
+    non-finite logp -> divergence), never an exception."""
+    return all(math.isfinite(v) and abs(v) < 300.0 for v in theta)
+
+
+def single_launch_ok(bound, M, want_gz=False):
+    """The bound evaluates this shape in one launch (``CollapsedBound._small_ok``; a test double without one never does)."""
+    return hasattr(bound, "_small_ok") and bound._small_ok(M, want_gz=want_gz)
+
+
+def single_launch_eval(bound, Z, theta, n_grad, want_gz=False, composite=None):
+    """ONE launch: transforms, priors, Jacobians and the chain rule are applied on the device (mode SGP_SMALL_HMC).
+    Returns (logp, its first ``n_grad`` gradients, dF/dZ device tensor or None), or None where the factorisation failed."""
+    h, info, gz = bound._small_eval(Z, theta, 1, True, want_gz, composite)
+    bound.n_evals += 1
+    bound.n_grads += 1
+    hl = h.tolist()
+    if info != 0 or not math.isfinite(hl[0]):
+        return None
+    return hl[0], hl[1:1 + n_grad], gz
+
+
+def device_sampler_ok(bound, entry, M, want_gz=False, n_draws_total=None, max_treedepth=10):
+    """True when ``hmc.sample_nuts_device`` can run a target over ``bound``: the engine has the persistent kernel ``entry``, the
+    bound takes the single-launch path -- and, when the run length is given, its worst case (every tree at the depth limit)
+    stays inside that kernel's cumulative int counters (``device_run_fits``); the host-driven sampler over the same single
+    launch takes the longer runs."""
+    ok = hasattr(bound.engine, entry) and single_launch_ok(bound, M, want_gz)
+    return ok and (n_draws_total is None or device_run_fits(int(bound.X.shape[0]), n_draws_total, max_treedepth))
+
+
+# ---------------------------------------------------------------------------------------------
+# the [log ls, log sig_f, log sig_n] head: ls ~ Gamma(2, 1), sig_f ~ HalfCauchy(1), sig_n ~ HalfCauchy(1)
+# ---------------------------------------------------------------------------------------------
+def theta_prior(ls, sf, sn):
+    """(log prior, d/d ls list, d/d sig_f, d/d sig_n) in the constrained variables."""
+    lp = sum(math.log(v) - v for v in ls)
+    g_ls = [1.0 / v - 1.0 for v in ls]
+    lp += (_LOG_2_OVER_PI - math.log1p(sf * sf)) + (_LOG_2_OVER_PI - math.log1p(sn * sn))
+    return lp, g_ls, -2.0 * sf / (1.0 + sf * sf), -2.0 * sn / (1.0 + sn * sn)
+
+
+def theta_logp_and_grad(theta, ls, sf, sn, F, g_ls=None, g_sf2=None, g_s2=None, finite_grad=False):
+    """F(ls, sf^2, sn^2) and its gradients -> (logp, grad) in the unconstrained theta: + priors + log-Jacobians sum(theta);
+    d/d log v = v d/d v, + 1 from the Jacobian.  ``g_ls=None``: the value alone, (logp, None).  ``finite_grad``: a non-finite
+    gradient entry gives (-inf, zeros)."""
+    lp, pg_ls, pg_sf, pg_sn = theta_prior(ls, sf, sn)
+    logp = F + lp + sum(theta)
+    if g_ls is None:
+        return logp, None
+    grad = [ls[j] * (g_ls[j] + pg_ls[j]) + 1.0 for j in range(len(ls))]
+    grad.append(sf * (2.0 * sf * g_sf2 + pg_sf) + 1.0)
+    grad.append(sn * (2.0 * sn * g_s2 + pg_sn) + 1.0)
+    if finite_grad and not all(math.isfinite(v) for v in grad):
+        return -math.inf, [0.0] * len(grad)
+    return logp, grad
+
+
+class _LogThetaTarget:
+    """``start`` / ``constrain`` of a target whose position begins with the d + 2 log-transformed hyper-parameters."""
+
+    d: int
+
+    def start(self):
+        """PyMC3's test point in the unconstrained space: Gamma(2,1) -> mean 2, HalfCauchy(1) -> 1."""
+        return [math.log(2.0)] * self.d + [0.0, 0.0]
+
+    def constrain(self, theta):
+        th = [float(v) for v in theta]
+        return {"ls": [math.exp(v) for v in th[: self.d]], "sig_f": math.exp(th[self.d]), "sig_n": math.exp(th[self.d + 1])}
+
+
+# ---------------------------------------------------------------------------------------------
+# HMC target: VFE logp + priors + log-Jacobians  (reference models/bayesian_sgpr_hmc.py:60-71)
+# ---------------------------------------------------------------------------------------------
+class HmcTarget(_LogThetaTarget):
+    """logp(theta_unc) and its gradient, theta_unc = [log ls_1..d, log sig_f, log sig_n].
+
+    ls ~ Gamma(alpha=2, beta=1), sig_f ~ HalfCauchy(1), sig_n ~ HalfCauchy(1), all log-transformed
+    as PyMC3 does for positive variables; covariance sig_f**2 * ExpQuad(ls), noise sig_n, Kuu jitter
+    1e-6 (``stabilize``).  A failed Cholesky gives logp = -inf (PyMC3: ``on_error='nan'``), which the
+    sampler treats as a divergence, never an exception.
+    """
+
+    def __init__(self, bound: CollapsedBound, Z, gradient="parity"):
+        """gradient: "parity" (default) -- every gradient holds 1e-6 against the CPU path (north_star): where the streaming order's error
+        estimate is beyond 3 x its tolerance a leapfrog runs in the whitened order (74 instead of 49 ms at C5).
+        "sampler" -- opt-in for NUTS in such a region: the extended order serves value AND gradient as far as its VALUE holds (2^14 x the
+        tolerance; 55 ms per leapfrog at C5).  The energy still meets 1e-8 per datum; the force is the extended order's explicit-Phibar
+        gradient, off by up to ~1e-4 relative at the far end of that range (profiles/r04_extended_order_c5.jsonl) -- but a deterministic
+        function of theta: the tier of every evaluation is the one its OWN error estimate names (`strict`), never the guard's memory of
+        earlier evaluations.  Leapfrog with a deterministic approximate force is still volume preserving and reversible, and the
+        accept step uses the accurate energy, so the chain still targets the exact posterior (tests/test_posterior_pin.py holds the
+        mode to the same 4 MCSE pin as the default); only the acceptance rate pays for the force error."""
+        if gradient not in ("parity", "sampler"):
+            raise ValueError("gradient must be 'parity' or 'sampler'")
+        self.bound = bound
+        self.Z = bound._prep_Z(Z)
+        self.d = bound.d
+        self.ndim = self.d + 2
+        self.gradient = gradient
+
+    def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
+        """True when ``hmc.sample_nuts_device`` can run this target (``sgp_small_nuts``; see ``targets.device_sampler_ok``)."""
+        return device_sampler_ok(self.bound, "small_nuts", self.Z.shape[0], False, n_draws_total, max_treedepth)
+
+    def run_on_device(self, q0, tune, n_samples, rng_state, **sampler_opts):
+        b = self.bound
+        return b.engine.small_nuts(b.X, b.y, self.Z, q0, tune, n_samples, rng_state, jitter=b.jitter, kernel=b.kernel, **sampler_opts)
+
+    def logp(self, theta):
+        theta = as_floats(theta)
+        if not in_range(theta):
+            return -math.inf
+        if single_launch_ok(self.bound, self.Z.shape[0]):
+            return self.logp_and_grad(theta)[0]
+        p = self.constrain(theta)  # the value alone: no gradient pass
+        F, parts = self.bound.value(self.Z, p["ls"], p["sig_f"] ** 2, p["sig_n"] ** 2, raise_on_fail=False,
+                                    **({"strict": True} if self.gradient == "sampler" else {}))
+        if parts.get("info", 0) != 0 or not math.isfinite(F):
+            return -math.inf
+        return theta_logp_and_grad(theta, p["ls"], p["sig_f"], p["sig_n"], F)[0]
+
+    def logp_and_grad(self, theta):
+        """Returns (logp, grad list[d+2]).  One call = one HMC leapfrog's worth of device work."""
+        theta = as_floats(theta)
+        bad = (-math.inf, [0.0] * self.ndim)
+        if not in_range(theta):
+            return bad
+        b = self.bound
+        if single_launch_ok(b, self.Z.shape[0]):
+            r = single_launch_eval(b, self.Z, theta, self.ndim)
+            return bad if r is None else r[:2]
+        p = self.constrain(theta)
+        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+        kw = {"grad_reach": b.extended_range, "strict": True} if self.gradient == "sampler" else {}
+        F, g = b.value_and_grad(self.Z, ls, sf * sf, sn * sn, want_gz=False, raise_on_fail=False, **kw)
+        if g.get("info", 0) != 0 or not math.isfinite(F):
+            return bad
+        # (one conversion of g["ls"]: indexing a tensor element by element costs ~1.5 us each -- 27 us per leapfrog at d = 18)
+        return theta_logp_and_grad(theta, ls, sf, sn, F, g["ls"].tolist(), g["sf2"], g["s2"])
+
+
+# ---------------------------------------------------------------------------------------------
+# exact-GP HMC target  (reference models/gpr_hmc.py:43-59)
+# ---------------------------------------------------------------------------------------------
+EXACT_MAX_N = 4096  # SGP_MAX_INDUCING: the largest N sgp_exact_eval factors
+
+
+class ExactHmcTarget(_LogThetaTarget):
+    """logp(theta_unc) and its gradient for NUTS over the EXACT GP marginal likelihood, theta_unc = [log ls_1..d, log sig_f, log sig_n].
+
+    ``pm.gp.Marginal(cov_func=sig_f**2 * ExpQuad(ls)).marginal_likelihood(y, X, noise=sig_n)`` with ls ~ Gamma(2, 1), sig_f ~
+    HalfCauchy(1), sig_n ~ HalfCauchy(1), log-transformed: the density is log N(y | 0, K + (sig_n^2 + jitter) I) plus
+    ``HmcTarget``'s priors and log-Jacobians.  ``jitter`` defaults to 0: Marginal adds only WhiteNoise(sig_n) to the diagonal.
+    One ``logp_and_grad`` is one ``engine.exact_eval`` (include/sgp.h: sgp_exact_eval) and one device-to-host copy.  A non-zero
+    status word (A numerically not positive definite, the conditioning gate), a non-finite F or a non-finite gradient entry gives
+    (-inf, zeros), which the sampler treats as a divergence; it never raises.  Single process: the target makes no collectives
+    (N <= 4096 fits one device)."""
+
+    def __init__(self, X, y, kernel="rbf", engine=None, jitter=0.0):
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine(X.device if X.is_cuda else None)
+        if kernel not in ("rbf", "matern32", "matern52"):
+            raise ValueError("ExactHmcTarget takes 'rbf', 'matern32' or 'matern52' (got %r)" % (kernel,))
+        self.engine = engine
+        if X.dim() == 1:
+            X = X[:, None]
+        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
+        self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
+        if self.X.shape[0] != self.y.shape[0]:
+            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
+        if self.X.shape[0] > EXACT_MAX_N:
+            raise ValueError("the exact GP takes at most N = %d training rows (got %d)" % (EXACT_MAX_N, self.X.shape[0]))
+        self.kernel = kernel
+        self.jitter = float(jitter)
+        self.d = int(self.X.shape[1])
+        self.ndim = self.d + 2
+        self.n_evals = 0
+
+    def _eval(self, theta, want_grad):
+        """(logp, grad or None) at theta."""
+        theta = as_floats(theta)
+        bad = (-math.inf, [0.0] * self.ndim if want_grad else None)
+        if not in_range(theta):
+            return bad
+        p = self.constrain(theta)
+        ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+        self.n_evals += 1
+        r = self.engine.exact_eval(self.X, self.y, ls, sf * sf, sn * sn + self.jitter, kernel=self.kernel, want_grad=want_grad)
+        if r["info"] != 0 or not math.isfinite(r["F"]):
+            return bad
+        if not want_grad:
+            return theta_logp_and_grad(theta, ls, sf, sn, r["F"])
+        return theta_logp_and_grad(theta, ls, sf, sn, r["F"], r["ls"], r["sf2"], r["s2"], finite_grad=True)
+
+    def logp(self, theta):
+        return self._eval(theta, False)[0]
+
+    def logp_and_grad(self, theta):
+        """Returns (logp, grad list[d+2])."""
+        return self._eval(theta, True)
+
+
+# ---------------------------------------------------------------------------------------------
+# joint HMC target: theta AND the inducing inputs  (reference models/all_in_HMC.py:45-61)
+# ---------------------------------------------------------------------------------------------
+class JointHmcTarget(_LogThetaTarget):
+    """logp(q) and its gradient for NUTS over the hyper-parameters and the inducing inputs together,
+    q = [log ls_1..d, log sig_f, log sig_n, vec(Z)] with Z row-major M x d, untransformed (ndim = d + 2 + M d).
+
+    The same VFE ``MarginalSparse`` density and theta priors / Jacobians as ``HmcTarget``, plus Z ~ Normal(0, 1)
+    elementwise with its normalising constants, so ``logp`` is PyMC3's model logp.  Kuu jitter 1e-6 (``stabilize``).
+    A value of theta outside the representable range or a failed factorisation gives -inf, never an exception."""
+
+    def __init__(self, bound: CollapsedBound, M: int):
+        if bound.kernel == "composite":
+            raise ValueError("the joint target takes stationary kernels (no dF/dZ for composite kernels)")
+        self.bound = bound
+        self.d = bound.d
+        self.M = int(M)
+        self.ndim = self.d + 2 + self.M * self.d
+
+    def start(self):
+        """PyMC3's test point: HmcTarget's for theta, the prior mean 0 for Z."""
+        return super().start() + [0.0] * (self.M * self.d)
+
+    def device_sampler_ok(self, n_draws_total=None, max_treedepth=10):
+        """True when ``hmc.sample_nuts_device`` can run this target (``sgp_small_nuts_joint``: the single-launch class with dF/dZ;
+        see ``targets.device_sampler_ok``)."""
+        return device_sampler_ok(self.bound, "small_nuts_joint", self.M, True, n_draws_total, max_treedepth)
+
+    def run_on_device(self, q0, tune, n_samples, rng_state, **sampler_opts):
+        b = self.bound  # (Z is part of the position)
+        return b.engine.small_nuts_joint(b.X, b.y, self.M, q0, tune, n_samples, rng_state, jitter=b.jitter, kernel=b.kernel, **sampler_opts)
+
+    def _split(self, q):
+        q = as_floats(q)
+        return q[:self.d + 2], q[self.d + 2:]
+
+    def constrain(self, q):
+        th, z = self._split(q)
+        return dict(super().constrain(th), Z=np.asarray(z, dtype=np.float64).reshape(self.M, self.d))
+
+    def logp(self, q):
+        return self.logp_and_grad(q)[0]
+
+    def logp_and_grad(self, q):
+        """Returns (logp, grad list[ndim]).  One call = one leapfrog's evaluation, dF/dZ included."""
+        th, z = self._split(q)
+        bad = (-math.inf, [0.0] * self.ndim)
+        if not in_range(th) or not all(math.isfinite(v) for v in z):
+            return bad
+        b = self.bound
+        zz = np.asarray(z, dtype=np.float64)
+        Zt = torch.from_numpy(zz.reshape(self.M, self.d)).to(b.engine.device)
+        zprior = -0.5 * float(zz @ zz) - _HALF_LOG_2PI * zz.size
+        if single_launch_ok(b, self.M, want_gz=True):
+            r = single_launch_eval(b, Zt, th, self.d + 2, want_gz=True)
+            if r is None:
+                return bad
+            logp, grad, gz = r
+        else:
+            p = super().constrain(th)
+            ls, sf, sn = p["ls"], p["sig_f"], p["sig_n"]
+            F, g = b.value_and_grad(Zt, ls, sf * sf, sn * sn, want_gz=True, raise_on_fail=False)
+            if g.get("info", 0) != 0 or not math.isfinite(F):
+                return bad
+            logp, grad = theta_logp_and_grad(th, ls, sf, sn, F, g["ls"].tolist(), g["sf2"], g["s2"])
+            gz = g["Z"]
+        return logp + zprior, grad + (gz.detach().to("cpu").numpy().reshape(-1) - zz).tolist()

@@ -325,7 +325,7 @@ def test_composite_device_resident_nuts_matches_the_host_driven_sampler(engine):
     q0 = np.array(tgt.start()) + 0.05
     tune, draws, seed = 15, 10, 77
     r = engine.small_nuts(X, yd, Z, q0, tune, draws, seed, jitter=1e-6, kernel="composite", max_treedepth=6,
-                          **tgt.device_sampler_args())
+                          composite=tgt.device_description())
     assert r["info"] == 0 and r["draws"] == tune + draws
     nuts = NUTS(tgt.logp_and_grad, tgt.ndim, max_treedepth=6, rng=SplitMix(seed))
     q = q0.copy()
@@ -377,7 +377,7 @@ def test_composite_single_launch_two_tile_size_class(engine):
     assert abs(lp1 - lp2) < 1e-8 * max(1.0, abs(lp2))
     assert np.max(np.abs(np.array(gr1) - np.array(gr2))) < 1e-6 * max(1.0, np.max(np.abs(gr2)))
     r = engine.small_nuts(X, yd, Zd, np.array(th), 8, 8, 5, jitter=1e-6, kernel="composite", max_treedepth=4,
-                          **tgt.device_sampler_args())
+                          composite=tgt.device_description())
     assert r["info"] == 0 and r["draws"] == 16 and np.all(np.isfinite(r["samples"].numpy()))
 
 
