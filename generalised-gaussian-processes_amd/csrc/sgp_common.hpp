@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include "../../include/sgp.h"
 
 namespace sgp {
@@ -29,6 +30,21 @@ struct KernArgs {
   double sf2;
   int d;
 };
+// inv_ls: d host doubles (NULL where the kernel does not read them: the composite kernel's parameters travel separately)
+inline KernArgs make_kern_args(const double* inv_ls, double sf2, int d) {
+  KernArgs ka;
+  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = (inv_ls && j < d) ? inv_ls[j] : 0.0;
+  ka.sf2 = sf2;
+  ka.d = d;
+  return ka;
+}
+
+// An integer tuning / A/B knob from the environment.  Callers keep the value in a function-local static (read once per process) or in
+// their context (read once per context).
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // exp(x) for the kernel profiles (x <= 0 there; correct for any finite x, saturating to 0 below -745): range reduction
 // x = k ln2 + r with the two-part ln2 of fdlibm, Taylor polynomial of degree 13 on |r| <= ln2 / 2 (remainder 4e-18

@@ -7,11 +7,6 @@
 
 namespace sgp {
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 static void ctx_init(Ctx& c, int device) {
   c.device = device;
   c.contraction = env_int("SGP_CONTRACTION", 1);

@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tall_kernel(const double* __restr
 }
 // SGP_GEMM_TALL=0 switches the kernel off (A/B); rows from which it is used
 static int gemm_tall_min_rows() {
-  static const int v = getenv("SGP_GEMM_TALL") ? atoi(getenv("SGP_GEMM_TALL")) : 16384;  // >= 128 workgroups of >= 1 row block
+  static const int v = env_int("SGP_GEMM_TALL", 16384);  // >= 128 workgroups of >= 1 row block
   return v;
 }
 static bool gemm_tall(const GemmDesc& g, hipStream_t st) {
@@ -452,7 +452,7 @@ static bool gemm_tall(const GemmDesc& g, hipStream_t st) {
   else if (g.klo_mask != 0 || g.khi_mask != 0) return false;
   const int nrb = g.m / TT, ncb = g.n / TT;
   // row blocks per workgroup: ~4 rounds of the 512 resident workgroups when there are that many row blocks, one block each otherwise
-  static const int rounds = getenv("SGP_GEMM_TALL_ROUNDS") ? atoi(getenv("SGP_GEMM_TALL_ROUNDS")) : 4;  // tuning knob
+  static const int rounds = env_int("SGP_GEMM_TALL_ROUNDS", 4);  // tuning knob
   int per = (nrb + 512 * rounds - 1) / (512 * rounds);
   if (per < 1) per = 1;
   const int grid = (nrb + per - 1) / per;
@@ -462,7 +462,7 @@ static bool gemm_tall(const GemmDesc& g, hipStream_t st) {
 
 // 64 x 64 tilings with at most this many tiles x 2 take the 32 x 32 tiles: the CU count (SGP_GEMM_SMALL_TILES=0 switches them off: A/B)
 static int gemm_small_tile_threshold() {
-  static const int v = getenv("SGP_GEMM_SMALL_TILES") ? atoi(getenv("SGP_GEMM_SMALL_TILES")) : 256;
+  static const int v = env_int("SGP_GEMM_SMALL_TILES", 256);
   return v;
 }
 void gemm(const GemmDesc& g, hipStream_t st) {
@@ -646,11 +646,11 @@ bool potrf_lower(double* A, double* Linv, int64_t ld, int Mp, int* info, int inf
   if (Linv && !(prepped & 2)) fill_zero(Linv, (size_t)Mp * ld, st);  // level 0 of tri_inverse(): diagonal-block inverses (written by the
                                                    // diagonal tile owners inside the launch), zero elsewhere
   // the chain-workgroup kernel from two block columns on, when at least one other workgroup can be resident beside it
-  static const int use_chain = getenv("SGP_POTRF_CHAIN") ? atoi(getenv("SGP_POTRF_CHAIN")) : 1;  // 0: the round-1 dataflow kernel (A/B); 2: the chain kernel for every nb >= 2
+  static const int use_chain = env_int("SGP_POTRF_CHAIN", 1);  // 0: the round-1 dataflow kernel (A/B); 2: the chain kernel for every nb >= 2
   // launch modes of the chain kernel (sgp_potrf_chain.hpp: CH_MODE_*), read once
-  static const int env_mode = ((getenv("SGP_POTRF_ACQUIRE") && atoi(getenv("SGP_POTRF_ACQUIRE"))) ? CH_MODE_ACQUIRE : 0) |
-                              ((getenv("SGP_POTRF_LIGHT") && !atoi(getenv("SGP_POTRF_LIGHT"))) ? CH_MODE_NOLIGHT : 0) |
-                              ((getenv("SGP_POTRF_TICKET") && atoi(getenv("SGP_POTRF_TICKET"))) ? CH_MODE_TICKET : 0);
+  static const int env_mode = (env_int("SGP_POTRF_ACQUIRE", 0) ? CH_MODE_ACQUIRE : 0) |
+                              (env_int("SGP_POTRF_LIGHT", 1) ? 0 : CH_MODE_NOLIGHT) |
+                              (env_int("SGP_POTRF_TICKET", 0) ? CH_MODE_TICKET : 0);
   // the ticketed claim where the caller says the GPU is shared (SGP_OPT_SHARED_DEVICE of the call's context; SGP_POTRF_TICKET=1 forces it)
   int mode = env_mode | (cur_ctx().shared_device ? CH_MODE_TICKET : 0);
   // The acquire-free consumer side (and the light same-XCD hand-overs) rest on "one writer per cache line, no reader before its flag":

@@ -1,6 +1,8 @@
 // Shared geometry of the two streaming passes (sgp_suffstats_fwd.hip / sgp_suffstats_bwd.hip).
 #pragma once
 #include <cstdlib>
+#include <initializer_list>
+#include <type_traits>
 #include "sgp_common.hpp"
 
 namespace sgp {
@@ -70,6 +72,14 @@ __host__ __device__ inline void split_range(const SplitMap& m, int split, int64_
   c1 = (cum0 + w) * nchunks / total;
 }
 
+// split map of `nchunks` units over `nsplit` splits: tapered where the plan says so (taper = NULL: equal splits)
+static inline SplitMap split_map(const int* taper, int64_t nchunks, int nsplit) {
+  const int cps = (int)((nchunks + nsplit - 1) / nsplit);
+  SplitMap m{{0, 0, 0, 0}, cps < 1 ? 1 : cps};
+  for (int l = 0; taper && l < 4; ++l) m.g[l] = taper[l];
+  return m;
+}
+
 static inline StreamPlan make_stream_plan(int64_t N, int M, int d) {
   StreamPlan p;
   p.Mp = padded_m(M);
@@ -85,20 +95,21 @@ static inline StreamPlan make_stream_plan(int64_t N, int M, int d) {
     const int64_t base = (p.Npad / ASM_ROWS) * ((p.Mp + 255) / 256);
     p.asm_sub = base < 128 ? 8 : (base < 256 ? 4 : 1);
   }
-  static const int asm_sub_override = getenv("SGP_ASM_SUB") ? atoi(getenv("SGP_ASM_SUB")) : 0;  // tuning knob: 1, 4, 8 or 16
+  static const int asm_sub_override = env_int("SGP_ASM_SUB", 0);  // tuning knob: 1, 4, 8 or 16
   if (asm_sub_override == 1 || asm_sub_override == 4 || asm_sub_override == 8 || asm_sub_override == 16) p.asm_sub = asm_sub_override;
   int64_t cap = (int64_t)(stream_kfu_budget() / ((size_t)p.Mp * 8)) / ASM_ROWS * ASM_ROWS;
   if (cap < ASM_ROWS) cap = ASM_ROWS;
   p.sc_rows = p.Npad < cap ? p.Npad : cap;
   const int64_t nchunks = p.sc_rows / NB;
-  static const int target_wgs = getenv("SGP_TARGET_WGS") ? atoi(getenv("SGP_TARGET_WGS")) : TARGET_WGS;  // tuning knob
+  static const int target_wgs = env_int("SGP_TARGET_WGS", TARGET_WGS);  // tuning knob
+  const bool target_wgs_set = getenv("SGP_TARGET_WGS") != nullptr;      // a presence test: set-but-empty counts, and it switches the rules below off
   int64_t k = (target_wgs + 8 * p.ntiles - 1) / (8 * p.ntiles);
   int64_t ns = 8 * k;
   // Wave quantisation: workgroups take 3.3-4.7 ms each at C5 and 512 run at a time, so a launch whose last round is
   // half empty idles a tenth of the chip (per-workgroup stamps: 14.9 ms of work in a 16.5 ms launch at 3.94 rounds).
   // With enough rows, take the split count (multiple of 8, 6-11 rounds of workgroups that still get >= 64 chunks
   // each) whose last round is fullest: 128 splits = exactly 9 rounds at M = 1024 (17.6 vs 18.5 ms on one box).
-  if (nchunks >= 64 * 8 && !getenv("SGP_TARGET_WGS")) {
+  if (nchunks >= 64 * 8 && !target_wgs_set) {
     double best_waste = 2.0;
     for (int64_t kk = (3072 + 8 * p.ntiles - 1) / (8 * p.ntiles); 8 * kk * p.ntiles <= 5632; ++kk) {
       const int64_t cand = 8 * kk;
@@ -118,19 +129,19 @@ static inline StreamPlan make_stream_plan(int64_t N, int M, int d) {
   // (round 5: 0.8 of a round, rounded DOWN -- the K_uu factorization's workgroups hold a quarter of the CUs' LDS while this kernel runs, and a
   // launch that does not fit beside them pays a second round: 56 / 48 / 40 / 32 / 24 splits at C3 = 104 / 106 / 89 / 105 / 136 us + a reduction
   // of 15 / 13 / 11 / 9 / 8 us, rocprofv3, same box)
-  if (nchunks / ns < 16 && !getenv("SGP_TARGET_WGS")) {
+  if (nchunks / ns < 16 && !target_wgs_set) {
     int64_t one_round = 8 * ((RESIDENT_WGS * 4 / 5) / (8 * p.ntiles));
     if (one_round < 8) one_round = 8;
     if (one_round < ns) ns = one_round;
   }
-  static const int ns_override = getenv("SGP_SYRK_NSPLIT") ? atoi(getenv("SGP_SYRK_NSPLIT")) : 0;  // tuning knob
+  static const int ns_override = env_int("SGP_SYRK_NSPLIT", 0);  // tuning knob
   if (ns_override > 0) ns = 8 * ((ns_override + 7) / 8);
   const int64_t lim = round_up64(nchunks > 0 ? nchunks : 1, 8);
   if (ns > lim) ns = lim;
   p.nsplit = (int)ns;
   p.taper[0] = p.taper[1] = p.taper[2] = p.taper[3] = 0;
-  static const int taper_on = getenv("SGP_SYRK_TAPER") ? atoi(getenv("SGP_SYRK_TAPER")) : 1;  // A/B knob (20.55 vs 20.76 ms)
-  if (taper_on && !getenv("SGP_TARGET_WGS") && ns % 32 == 0 && nchunks / ns >= 64) {
+  static const int taper_on = env_int("SGP_SYRK_TAPER", 1);  // A/B knob (20.55 vs 20.76 ms)
+  if (taper_on && !target_wgs_set && ns % 32 == 0 && nchunks / ns >= 64) {
     // big splits first, then halves, quarters and eighths: the last round of workgroups is short, so the ragged end of
     // the launch (workgroup durations differ by +-15 %) shrinks with it
     const int B = (int)(ns / 8);
@@ -144,19 +155,63 @@ static inline StreamPlan make_stream_plan(int64_t N, int M, int d) {
     const int64_t one_round = 8 * ((RESIDENT_WGS + 8 * p.nmb - 1) / (8 * p.nmb));
     if (one_round < nsb) nsb = one_round;
   }
-  static const int nsb_override = getenv("SGP_KBAR_NSPLIT") ? atoi(getenv("SGP_KBAR_NSPLIT")) : 0;  // tuning knob
+  static const int nsb_override = env_int("SGP_KBAR_NSPLIT", 0);  // tuning knob
   if (nsb_override > 0) nsb = 8 * ((nsb_override + 7) / 8);
   const int64_t limb = round_up64(nblocks > 0 ? nblocks : 1, 8);
   if (nsb > limb) nsb = limb;
   p.nsplit_b = (int)nsb;
   p.taper_b[0] = p.taper_b[1] = p.taper_b[2] = p.taper_b[3] = 0;
-  static const int taper_b_on = getenv("SGP_KBAR_TAPER") ? atoi(getenv("SGP_KBAR_TAPER")) : 1;  // A/B knob (55.4 vs 56.2 ms)
+  static const int taper_b_on = env_int("SGP_KBAR_TAPER", 1);  // A/B knob (55.4 vs 56.2 ms)
   if (taper_b_on && nsb % 32 == 0 && nblocks / nsb >= 8) {
     const int B = (int)(nsb / 8);
     p.taper_b[0] = 3 * B / 4; p.taper_b[1] = B / 4; p.taper_b[2] = B / 4; p.taper_b[3] = B / 2;
     p.nsplit_b = 8 * (p.taper_b[0] + p.taper_b[1] + p.taper_b[2] + p.taper_b[3]);
   }
   return p;
+}
+
+// ---- the host-side frame of the row-streaming entry points: check, plan, carve, prologue, their own launches, epilogue ----------
+// The checks every one of them starts with, in the order the status codes promise: SGP_ERR_ARG (a NULL among `required`, the entry
+// point's own non-optional pointers; shapes; the data rows of a non-empty shard; the kernel id) before SGP_ERR_DIM.  Checks only one
+// entry point has (all of them SGP_ERR_ARG) stand in front of this call; SGP_ERR_WORKSPACE follows it, after the carve.
+static inline int check_stream_args(std::initializer_list<const void*> required, const double* X, int64_t ldx, const double* y, int64_t ldz,
+                                    int64_t N, int M, int d, int kernel_id, bool composite_ok) {
+  for (const void* ptr : required)
+    if (!ptr) return SGP_ERR_ARG;
+  if (N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
+  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
+  if (kernel_id < 0 || kernel_id > SGP_KERNEL_COMPOSITE || (kernel_id == SGP_KERNEL_COMPOSITE && !composite_ok)) return SGP_ERR_ARG;
+  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  return SGP_OK;
+}
+// the shapes the workspace queries answer for (0 bytes otherwise)
+static inline bool stream_shape_ok(int64_t N, int M, int d) { return N >= 0 && M > 0 && d > 0 && d <= SGP_MAX_DIM && M <= SGP_MAX_INDUCING; }
+
+// for (auto [r0, rows] : SuperChunks{Npad, step}): the row ranges [r0, r0 + rows) of Npad rows, `step` at a time, the last one short
+struct SuperChunks {
+  int64_t Npad, step;
+  struct Range { int64_t r0, rows; };
+  struct It {
+    int64_t r0, Npad, step;
+    Range operator*() const { return {r0, Npad - r0 < step ? Npad - r0 : step}; }
+    void operator++() { r0 += step; }
+    bool operator!=(const It&) const { return r0 < Npad; }
+  };
+  It begin() const { return {0, Npad, step}; }
+  It end() const { return {Npad, Npad, step}; }
+};
+
+// f(std::integral_constant<int, DP>()) for the padded dimension of a plan (dp_for(): 2, 4, 8, 16, 24 or 32)
+template <typename F>
+static inline void dispatch_dp(int DP, F&& f) {
+  switch (DP) {
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    case 24: f(std::integral_constant<int, 24>()); break;
+    default: f(std::integral_constant<int, 32>()); break;
+  }
 }
 
 // Optional per-kernel timing (sgp_timing_enable): HIP events recorded on the launch stream around the

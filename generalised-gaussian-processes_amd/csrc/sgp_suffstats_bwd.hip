@@ -444,23 +444,37 @@ static BwdWs carve_bwd(void* ws, const StreamPlan& p, bool need_kfu) {
   return w;
 }
 
-template <int DP, bool KP = true>
-static void launch_bwd(int kid, int grid, hipStream_t st, const double* Kfu, const BwdWs& w, double sf2, int64_t row0,
-                       int64_t nblocks, int bps, int64_t N, int M, const StreamPlan& p, int want_gz, int accumulate) {
-  const SplitMap bmap{{p.taper_b[0], p.taper_b[1], p.taper_b[2], p.taper_b[3]}, bps};
-#define SGP_BWD_ARGS Kfu, w.Xs, w.ys, w.Zs, w.Pb, w.bb, sf2, row0, nblocks, bmap, N, M, p.Mp, p.nmb, want_gz, accumulate, w.gacc, w.gzpart, w.glpart
-  switch (kid) {
-#define SGP_BWD_LAUNCH(K) \
+// The contraction of pass 2 over `nblocks` 128-row blocks of K (KP: K is K'_fu itself and the kernel multiplies by Phibar; otherwise K
+// arrives as a product with the factors in front of the last one already applied)
+template <bool KP>
+static void launch_kbar(const StreamPlan& p, int kid, const double* K, const BwdWs& w, double sf2, int64_t row0, int64_t nblocks, int64_t N,
+                        int M, int want_gz, int accumulate, hipStream_t st) {
+  const int grid = p.nmb * p.nsplit_b;
+  const SplitMap bmap = split_map(p.taper_b, nblocks, p.nsplit_b);
+#define SGP_BWD_ARGS K, w.Xs, w.ys, w.Zs, w.Pb, w.bb, sf2, row0, nblocks, bmap, N, M, p.Mp, p.nmb, want_gz, accumulate, w.gacc, w.gzpart, w.glpart
+#define SGP_BWD_LAUNCH(KID) \
   do { \
-    if (want_gz) kbar_contract_kernel<DP, K, true, KP><<<grid, 256, 0, st>>>(SGP_BWD_ARGS); \
-    else kbar_contract_kernel<DP, K, false, KP><<<grid, 256, 0, st>>>(SGP_BWD_ARGS); \
+    if (want_gz) kbar_contract_kernel<DP, KID, true, KP><<<grid, 256, 0, st>>>(SGP_BWD_ARGS); \
+    else kbar_contract_kernel<DP, KID, false, KP><<<grid, 256, 0, st>>>(SGP_BWD_ARGS); \
   } while (0)
-    case SGP_KERNEL_RBF: SGP_BWD_LAUNCH(SGP_KERNEL_RBF); break;
-    case SGP_KERNEL_MATERN32: SGP_BWD_LAUNCH(SGP_KERNEL_MATERN32); break;
-    default: SGP_BWD_LAUNCH(SGP_KERNEL_MATERN52); break;
-  }
+  dispatch_dp(p.DP, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    switch (kid) {
+      case SGP_KERNEL_RBF: SGP_BWD_LAUNCH(SGP_KERNEL_RBF); break;
+      case SGP_KERNEL_MATERN32: SGP_BWD_LAUNCH(SGP_KERNEL_MATERN32); break;
+      default: SGP_BWD_LAUNCH(SGP_KERNEL_MATERN52); break;
+    }
+  });
 #undef SGP_BWD_LAUNCH
 #undef SGP_BWD_ARGS
+}
+// g_ls, g_sf2 and g_Z from the partials of the contraction, in a fixed order
+static void finish_grads(const StreamPlan& p, const BwdWs& w, const KernArgs& ka, double kappabar, int64_t N, int M, double* g_ls,
+                         double* g_sf2, double* g_Z, hipStream_t st) {
+  const int64_t tot = (int64_t)M * ka.d;
+  const int rg = (int)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024);
+  bwd_reduce_kernel<<<rg < 1 ? 1 : rg, 256, 0, st>>>(w.gzpart, w.glpart, p.nsplit_b, p.nmb, p.Mp, M, p.DP, ka, kappabar * (double)N, g_ls,
+                                                    g_sf2, g_Z);
 }
 
 }  // namespace sgp
@@ -468,7 +482,7 @@ static void launch_bwd(int kid, int grid, hipStream_t st, const double* Kfu, con
 using namespace sgp;
 
 static size_t bwd_workspace_bytes(int64_t N, int M, int d, bool library_kfu) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p = make_stream_plan(N, M, d);
   const size_t fast = carve_bwd(nullptr, p, library_kfu).bytes;
   const size_t comp = d <= COMP_MAX_DIM ? comp_bwd_workspace_bytes(N, M, d) : 0;  // one size for every kernel_id
@@ -484,10 +498,7 @@ extern "C" int sgp_suffstats_bwd(const double* X, int64_t ldx, const double* y, 
                                  double kappabar, const double* Kfu_in, int64_t N, int M, int d, int kernel_id,
                                  double* g_ls, double* g_sf2, double* g_Z, void* ws, size_t ws_bytes,
                                  sgp_stream_t stream) {
-  if (!Z || !inv_ls || !Phibar || !bbar || !g_ls || !g_sf2 || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  if (const int bad = check_stream_args({Z, inv_ls, Phibar, bbar, g_ls, g_sf2}, X, ldx, y, ldz, N, M, d, kernel_id, true)) return bad;
   if (kernel_id == SGP_KERNEL_COMPOSITE) {  // g_ls receives the SGP_COMP_LEN-double gradient block, g_sf2 = 0
     CompSpec cs;
     if (comp_parse(inv_ls, d, &cs) != SGP_OK) return SGP_ERR_ARG;
@@ -501,12 +512,7 @@ extern "C" int sgp_suffstats_bwd(const double* X, int64_t ldx, const double* y, 
   BwdWs w = carve_bwd(ws, p, Kfu_in == nullptr);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   {  // one launch: the scaled rows of both passes' prologue and pass 2's padded, symmetrised Phibar / bbar
     PadSymJob pad;
     pad.P = Phibar; pad.out = w.Pb; pad.vec = bbar; pad.vout = w.bb;
@@ -514,35 +520,18 @@ extern "C" int sgp_suffstats_bwd(const double* X, int64_t ldx, const double* y, 
   }
 
   const int want_gz = g_Z != nullptr;
-  const int grid = p.nmb * p.nsplit_b;
-  auto launch = [&](const double* Kfu, int64_t row0, int64_t nblocks, int accumulate) {
-    int bps = (int)((nblocks + p.nsplit_b - 1) / p.nsplit_b);
-    if (bps < 1) bps = 1;
-    switch (p.DP) {
-      case 2: launch_bwd<2>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-      case 4: launch_bwd<4>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-      case 8: launch_bwd<8>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-      case 16: launch_bwd<16>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-      case 24: launch_bwd<24>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-      default: launch_bwd<32>(kernel_id, grid, st, Kfu, w, sf2, row0, nblocks, bps, N, M, p, want_gz, accumulate); break;
-    }
-  };
-  if (p.Npad == 0) launch(nullptr, 0, 0, 0);  // empty shard: writes zero partials
-  for (int64_t r0 = 0; r0 < p.Npad; r0 += p.sc_rows) {
-    const int64_t rows = (p.Npad - r0) < p.sc_rows ? (p.Npad - r0) : p.sc_rows;
+  if (p.Npad == 0) launch_kbar<true>(p, kernel_id, nullptr, w, sf2, 0, 0, N, M, want_gz, 0, st);  // empty shard: writes zero partials
+  for (auto [r0, rows] : SuperChunks{p.Npad, p.sc_rows}) {
     const double* Kfu = Kfu_in ? Kfu_in + r0 * p.Mp : nullptr;
     if (!Kfu_in) {
       stream_assemble(p, kernel_id, w.Xs, w.ys, w.Zs, r0, rows, N, M, w.Kfu, w.bpart, st);
       Kfu = w.Kfu;
     }
     timing_begin(TIMING_KBAR, st);
-    launch(Kfu, r0, rows / TILE, r0 > 0 ? 1 : 0);
+    launch_kbar<true>(p, kernel_id, Kfu, w, sf2, r0, rows / TILE, N, M, want_gz, r0 > 0 ? 1 : 0, st);
     timing_end(TIMING_KBAR, st);
   }
-  const int64_t tot = (int64_t)M * d;
-  const int rg = (int)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024);
-  bwd_reduce_kernel<<<rg < 1 ? 1 : rg, 256, 0, st>>>(w.gzpart, w.glpart, p.nsplit_b, p.nmb, p.Mp, M, p.DP, ka,
-                                                    kappabar * (double)N, g_ls, g_sf2, g_Z);
+  finish_grads(p, w, ka, kappabar, N, M, g_ls, g_sf2, g_Z, st);
   return check_launch();
 }
 
@@ -554,12 +543,12 @@ extern "C" int sgp_suffstats_bwd(const double* X, int64_t ldx, const double* y, 
 // CollapsedBound), the third product inside kbar_contract_kernel (Pb = L^-1 / 2, epilogue recomputing k').
 // SGP_BWD_FULLY_FACTORED=1 keeps the three-product chain (A/B, accuracy studies); read once
 static int bwd_fully_factored() {
-  static const int v = getenv("SGP_BWD_FULLY_FACTORED") ? atoi(getenv("SGP_BWD_FULLY_FACTORED")) : 0;
+  static const int v = env_int("SGP_BWD_FULLY_FACTORED", 0);
   return v;
 }
 // caller_t: T1 = K'_fu L^-T arrives from pass 1 (sgp_suffstats_fwd_whitened_rows kept it): neither K'_fu nor T1 live in the workspace
 static size_t bwd_factored_workspace_bytes(int64_t N, int M, int d, bool caller_t) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p = make_stream_plan(N, M, d);
   p.sc_rows = p.Npad;
   const int nt = (caller_t ? 0 : 1) + (bwd_fully_factored() ? 1 : 0);
@@ -577,12 +566,8 @@ static int bwd_factored(const double* X, int64_t ldx, const double* y, const dou
                         const double* kuu_linv, const double* Cw, double s2, const double* bbar, double kappabar, int64_t N, int M,
                         int d, int kernel_id, const double* T_in, double* g_ls, double* g_sf2, double* g_Z, void* ws, size_t ws_bytes,
                         sgp_stream_t stream) {
-  if (!Z || !inv_ls || !kuu_linv || !Cw || !bbar || !g_ls || !g_sf2 || N < 0 || M <= 0 || d <= 0 || ldz < d || !(s2 > 0.0))
-    return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;
-  if (T_in && kernel_id == SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  if (!(s2 > 0.0) || (T_in && kernel_id == SGP_KERNEL_COMPOSITE)) return SGP_ERR_ARG;
+  if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, Cw, bbar, g_ls, g_sf2}, X, ldx, y, ldz, N, M, d, kernel_id, true)) return bad;
   hipStream_t st = (hipStream_t)stream;
   if (!ws || ws_bytes < bwd_factored_workspace_bytes(N, M, d, T_in != nullptr)) return SGP_ERR_WORKSPACE;
   if (kernel_id == SGP_KERNEL_COMPOSITE) {
@@ -606,11 +591,7 @@ static int bwd_factored(const double* X, int64_t ldx, const double* y, const dou
   // (inside kbar_contract_kernel) is left behind T1 = K'_fu L^-T instead of two: what must stay factored is L^-T ... L^-1 around the
   // whitened core (entries of size cond(K_uu) in the explicit Phibar); Q's are of size sqrt(cond), the same size the last factor
   // of the fully factored chain has anyway.
-
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
   bwd_pad_plain_kernel<<<2048, 256, 0, st>>>(kuu_linv, M, p.Mp, 0.5, fully ? w.Pb : Q0);  // the kernel forms 2 sf2 (T Pb)
   bwd_pad_small_kernel<<<2048, 256, 0, st>>>(Cw, M, p.Mp, 1.0 / s2, P2);
@@ -622,7 +603,6 @@ static int bwd_factored(const double* X, int64_t ldx, const double* y, const dou
   }
   bwd_pad_vec_kernel<<<(p.Mp + 255) / 256, 256, 0, st>>>(bbar, M, p.Mp, w.bb);
   const int want_gz = g_Z != nullptr;
-  const int grid = p.nmb * p.nsplit_b;
   const double* T1c = T_in ? T_in : T1;
   if (p.Npad > 0) {
     if (!T_in) {
@@ -643,24 +623,8 @@ static int bwd_factored(const double* X, int64_t ldx, const double* y, const dou
       gemm(g2, st);
     }
   }
-  const double* Tin = fully ? T2 : T1c;
-  {
-    const int64_t nblocks = p.Npad / TILE;
-    int bps = (int)((nblocks + p.nsplit_b - 1) / p.nsplit_b);
-    if (bps < 1) bps = 1;
-    switch (p.DP) {
-      case 2: launch_bwd<2, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-      case 4: launch_bwd<4, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-      case 8: launch_bwd<8, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-      case 16: launch_bwd<16, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-      case 24: launch_bwd<24, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-      default: launch_bwd<32, false>(kernel_id, grid, st, Tin, w, sf2, 0, nblocks, bps, N, M, p, want_gz, 0); break;
-    }
-  }
-  const int64_t tot = (int64_t)M * d;
-  const int rg = (int)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024);
-  bwd_reduce_kernel<<<rg < 1 ? 1 : rg, 256, 0, st>>>(w.gzpart, w.glpart, p.nsplit_b, p.nmb, p.Mp, M, p.DP, ka,
-                                                    kappabar * (double)N, g_ls, g_sf2, g_Z);
+  launch_kbar<false>(p, kernel_id, fully ? T2 : T1c, w, sf2, 0, p.Npad / TILE, N, M, want_gz, 0, st);
+  finish_grads(p, w, ka, kappabar, N, M, g_ls, g_sf2, g_Z, st);
   return check_launch();
 }
 

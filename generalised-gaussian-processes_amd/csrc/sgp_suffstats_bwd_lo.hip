@@ -674,7 +674,7 @@ static LoWs carve_lo(void* ws, const StreamPlan& p, bool have_f16 = false) {
 using namespace sgp;
 
 extern "C" size_t sgp_suffstats_bwd_lo_workspace_bytes_ex(int64_t N, int M, int d, int have_f16) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   return carve_lo(nullptr, make_stream_plan(N, M, d), have_f16 != 0).bytes;
 }
 extern "C" size_t sgp_suffstats_bwd_lo_workspace_bytes(int64_t N, int M, int d) { return sgp_suffstats_bwd_lo_workspace_bytes_ex(N, M, d, 0); }
@@ -695,10 +695,9 @@ extern "C" int sgp_suffstats_bwd_lo_f16(const double* X, int64_t ldx, const doub
                                         double sf2, const double* Phibar_lo, const double* Kfu_in, const uint16_t* Kfu_f16_in, int64_t N,
                                         int M, int d, int kernel_id, double* g_ls, double* g_sf2, double* delta, void* ws, size_t ws_bytes,
                                         sgp_stream_t stream) {
-  if (!Z || !inv_ls || !Phibar_lo || (!Kfu_in && !Kfu_f16_in) || !g_ls || !g_sf2 || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id != SGP_KERNEL_RBF) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  // its own rules stay its own: one of the two images of K'_fu (which of them the kernel picked below reads is not looked at here), RBF only
+  if ((!Kfu_in && !Kfu_f16_in) || kernel_id != SGP_KERNEL_RBF) return SGP_ERR_ARG;
+  if (const int bad = check_stream_args({Z, inv_ls, Phibar_lo, g_ls, g_sf2}, X, ldx, y, ldz, N, M, d, kernel_id, false)) return bad;
   if (N == 0) {
     if (delta) fill_zero(delta, (size_t)d + 1, (hipStream_t)stream);
     return check_launch();
@@ -708,13 +707,12 @@ extern "C" int sgp_suffstats_bwd_lo_f16(const double* X, int64_t ldx, const doub
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   const uint16_t* Kh = Kfu_f16_in ? Kfu_f16_in : w.Kh;
   hipStream_t st = (hipStream_t)stream;
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
-  static const int lo_kernel = getenv("SGP_LO_KERNEL") ? atoi(getenv("SGP_LO_KERNEL")) : 3;   // A/B: 1 = the first version (128 x 128 tiles, register ring, fp64 contraction)
-  if (lo_kernel != 3 && d > 8) return SGP_ERR_DIM;   // (the first version's kernel: d <= 8)
+  static const int lo_kernel = env_int("SGP_LO_KERNEL", 3);   // A/B: 1 = the first version (128 x 128 tiles, register ring, fp64 contraction)
+  // (the first version's kernel: d <= 8.  This return comes after the prologue has been enqueued, unlike every check of the shared
+  // frame: moving it is a change of behaviour on an error path and is left for a fix of its own)
+  if (lo_kernel != 3 && d > 8) return SGP_ERR_DIM;
   const bool v3 = lo_kernel == 3;
   const int NG = (p.DP + 7) / 8;
   const int Mp2 = (p.Mp + L3_T - 1) / L3_T * L3_T, plm = v3 ? Mp2 : p.Mp;   // the padded edge of the low word's image
@@ -732,7 +730,7 @@ extern "C" int sgp_suffstats_bwd_lo_f16(const double* X, int64_t ldx, const doub
     const int ncb2 = Mp2 / L3_T;
     nparts = (int)(((nrb2 + 7) / 8) * 8 * ncb2);
     part_dp = 8 * NG;
-    static const int lo_var = getenv("SGP_LO_VARIANT") ? atoi(getenv("SGP_LO_VARIANT")) : 0;
+    static const int lo_var = env_int("SGP_LO_VARIANT", 0);
     typedef void (*lo3_fn)(const uint16_t*, const uint16_t*, const lo_u4*, const float*, int, int, int, int64_t, int, double*);
     static const lo3_fn fns[3] = {kphi_lo3_kernel<0>, kphi_lo3_kernel<1>, kphi_lo3_kernel<2>};
     const lo3_fn fn = fns[lo_var < 0 || lo_var > 2 ? 0 : lo_var];

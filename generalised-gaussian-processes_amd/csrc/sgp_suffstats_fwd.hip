@@ -528,14 +528,7 @@ static void launch_assemble(int kid, int sub, dim3 grid, hipStream_t st, const d
 void stream_assemble(const StreamPlan& p, int kid, const double* Xs, const double* ys, const double* Zs, int64_t row0,
                      int64_t rows, int64_t N, int M, double* Kfu, double* bpart, hipStream_t st) {
   dim3 grid((unsigned)(rows / ASM_ROWS * p.asm_sub), (p.Mp + 255) / 256);
-  switch (p.DP) {
-    case 2: launch_assemble<2>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-    case 4: launch_assemble<4>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-    case 8: launch_assemble<8>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-    case 16: launch_assemble<16>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-    case 24: launch_assemble<24>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-    default: launch_assemble<32>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); break;
-  }
+  dispatch_dp(p.DP, [&](auto dp) { launch_assemble<decltype(dp)::value>(kid, p.asm_sub, grid, st, Xs, ys, Zs, row0, N, M, p.Mp, Kfu, bpart); });
 }
 
 void stream_prologue(const StreamPlan& p, const KernArgs& ka, const double* X, int64_t ldx, const double* y,
@@ -659,6 +652,26 @@ static void launch_syrk(const Ctx& cx, const double* K, int Mp, int64_t nchunks,
     if (skip_upper) SGP_SYRK_LAUNCH(4, false, true); else SGP_SYRK_LAUNCH(4, false, false);
   }
 #undef SGP_SYRK_LAUNCH
+}
+// the contraction over zero chunks: every slab tile of an empty shard is written (zeros)
+static void zero_slabs(const StreamPlan& p, const double* K, double* slab, hipStream_t st) {
+  syrk_tile_kernel<4, false, false><<<p.ntiles * p.nsplit, 256, 0, st>>>(K, p.Mp, 0, split_map(nullptr, 0, p.nsplit), p.ntiles, 0, slab, p.nsplit);
+}
+
+// The fixed-order tail of pass 1 over a workspace with bpart / btmp / yypart.  finish_b: b = sf2 K'^T y from `nparts` partials per
+// ASM_ROWS row block (the fp64 assembly leaves asm_sub of them, the integer path's assembly and tpart_kernel one), yy and kappa;
+// finish_stats: Phi = sf2^2 K'^T K' from `nslabs` slabs first.
+template <typename Ws>
+static void finish_b(const StreamPlan& p, const Ws& w, int nparts, double sf2, int64_t N, int M, double* b, double* yy, double* kappa,
+                     hipStream_t st) {
+  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(w.bpart, p.Npad / ASM_ROWS * nparts, p.Mp, BRED_G, w.btmp);
+  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.btmp, BRED_G, p.Mp, M, w.yypart, 256, sf2, sf2 * (double)N, b, yy, kappa);
+}
+static void finish_stats(const StreamPlan& p, const FwdWs& w, int nslabs, int nparts, double sf2, int64_t N, int M, double* Phi, double* b,
+                         double* yy, double* kappa, hipStream_t st) {
+  const int nb32 = p.Mp / 32;
+  reduce_phi_kernel<<<nb32 * (nb32 + 1) / 2, 256, 0, st>>>(w.slab, nslabs, p.ntiles, M, sf2 * sf2, Phi);
+  finish_b(p, w, nparts, sf2, N, M, b, yy, kappa, st);
 }
 
 // ---- whitened pass 1 in the streaming layout (round 4) ---------------------------------------------------------------------
@@ -806,11 +819,11 @@ __global__ __launch_bounds__(256) void dd_gemm_nt_kernel(const double* __restric
 }
 static void dd_launch(const double* Ahi, const double* Alo, const double* B, int n, double* Chi, double* Clo, int tr, hipStream_t st, int kmode,
                       int lower_only) {
-  static const int full = getenv("SGP_DD_FULL") ? atoi(getenv("SGP_DD_FULL")) : 0;   // A/B: the whole product, every tile (rounds 4-5)
+  static const int full = env_int("SGP_DD_FULL", 0);   // A/B: the whole product, every tile (rounds 4-5)
   if (full) { kmode = 0; lower_only = 0; }
   // SGP_DD_TILE=44: the 64 x 64 tiles of rounds 4-5.  Same box, Phibar's two products at n = 1024: 1.39-1.40 ms (64 x 64), 1.14-1.16 (64 x 32),
   // 1.06-1.07 (32 x 32: four waves per SIMD) -- profiles/r06_dd_gemm_tile_ab.txt
-  static const int shape = getenv("SGP_DD_TILE") ? atoi(getenv("SGP_DD_TILE")) : 22;
+  static const int shape = env_int("SGP_DD_TILE", 22);
   if (shape == 44) dd_gemm_nt_kernel<4, 4><<<dim3(n / 64, n / 64), 256, 0, st>>>(Ahi, Alo, B, n, Chi, Clo, tr, kmode, lower_only);
   else dd_gemm_nt_kernel<2, 2><<<dim3(n / 32, n / 32), 256, 0, st>>>(Ahi, Alo, B, n, Chi, Clo, tr, kmode, lower_only);
 }
@@ -968,7 +981,7 @@ extern "C" size_t sgp_kfu_len(int64_t N, int M) {
 }
 
 static size_t fwd_workspace_bytes(int64_t N, int M, int d, bool library_kfu) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p = make_stream_plan(N, M, d);
   const size_t fast = carve_fwd(nullptr, p, library_kfu, p.sc_rows).bytes, comp = comp_fwd_workspace_bytes(N, M);  // one size for every kernel_id
   return fast > comp ? fast : comp;
@@ -987,10 +1000,7 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
   Ctx& cx = cur_ctx();
   hipEvent_t gate = cx.pass1_gate;
   cx.pass1_gate = nullptr;
-  if (!Z || !inv_ls || !Phi || !b || !yy || !kappa || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  if (const int bad = check_stream_args({Z, inv_ls, Phi, b, yy, kappa}, X, ldx, y, ldz, N, M, d, kernel_id, true)) return bad;
   if (kernel_id == SGP_KERNEL_COMPOSITE) {  // inv_ls carries the parameter block; materialised path, Kfu_out unused
     CompSpec cs;
     if (comp_parse(inv_ls, d, &cs) != SGP_OK) return SGP_ERR_ARG;
@@ -1002,19 +1012,9 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
   FwdWs w = carve_fwd(ws, p, Kfu_out == nullptr, qrows);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-
-  stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
+  stream_prologue(p, make_kern_args(inv_ls, sf2, d), X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
   double* Kfu = Kfu_out ? Kfu_out : w.Kfu;
-  const int grid = p.ntiles * p.nsplit;
-  if (p.Npad == 0) {
-    // empty shard: run the contraction over zero chunks so every slab tile is written (zeros)
-    syrk_tile_kernel<4, false, false><<<grid, 256, 0, st>>>(Kfu, p.Mp, 0, SplitMap{{0, 0, 0, 0}, 1}, p.ntiles, 0, w.slab, p.nsplit);
-  }
+  if (p.Npad == 0) zero_slabs(p, Kfu, w.slab, st);
   auto contract = [&](const double* K, int64_t nchunks, const SplitMap& smap, int nsplit, int accum, double* slab) {
     launch_syrk(cx, K, p.Mp, nchunks, smap, p.ntiles, nsplit, accum, slab, st);
   };
@@ -1033,8 +1033,7 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
     // gradient: pass 2 reads the fp64 block) the assembly writes both and the planes take their own super-chunk of workspace.
     // The split count is that of a full super-chunk.
     const int ns = i8_nsplit(qrows, p.Mp);
-    for (int64_t r0 = 0; r0 < p.Npad; r0 += qrows) {
-      const int64_t rows = (p.Npad - r0) < qrows ? (p.Npad - r0) : qrows;
+    for (auto [r0, rows] : SuperChunks{p.Npad, qrows}) {
       timing_begin(TIMING_ASSEMBLE, st);
       i8_assemble(p, kernel_id, w.Xs, w.ys, w.Zs, r0, rows, N, M, w.Q, Kfu_out ? Kfu_out + (size_t)r0 * p.Mp : nullptr, w.bpart, st);
       timing_end(TIMING_ASSEMBLE, st);
@@ -1054,10 +1053,7 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
     const int64_t hrows = head_chunks * NB, trows = p.Npad - hrows, tchunks = trows / NB;
     const bool side = cx.asm_overlap == 1 && side_stream_ready(cx);
     double* head_slab = w.slab + (size_t)p.nsplit * p.ntiles * TILE * TILE;
-    const int hcps = (int)((head_chunks + head_ns - 1) / head_ns);
-    const int tcps = (int)((tchunks + p.nsplit - 1) / p.nsplit);
-    const SplitMap hmap{{0, 0, 0, 0}, hcps < 1 ? 1 : hcps};
-    const SplitMap tmap{{p.taper[0], p.taper[1], p.taper[2], p.taper[3]}, tcps < 1 ? 1 : tcps};
+    const SplitMap hmap = split_map(nullptr, head_chunks, head_ns), tmap = split_map(p.taper, tchunks, p.nsplit);
     timing_begin(TIMING_ASSEMBLE, st);
     stream_assemble(p, kernel_id, w.Xs, w.ys, w.Zs, 0, hrows, N, M, Kfu, w.bpart, st);
     bool forked = false;
@@ -1077,26 +1073,17 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
     cx.syrk_timed_rows = trows;
     nslabs = p.nsplit + head_ns;
   } else {
-    for (int64_t r0 = 0; r0 < p.Npad; r0 += p.sc_rows) {
-      const int64_t rows = (p.Npad - r0) < p.sc_rows ? (p.Npad - r0) : p.sc_rows;
+    for (auto [r0, rows] : SuperChunks{p.Npad, p.sc_rows}) {
       timing_begin(TIMING_ASSEMBLE, st);
       stream_assemble(p, kernel_id, w.Xs, w.ys, w.Zs, r0, rows, N, M, Kfu, w.bpart, st);
       timing_end(TIMING_ASSEMBLE, st);
-      const int64_t nchunks = rows / NB;
-      const int cps = (int)((nchunks + p.nsplit - 1) / p.nsplit);
-      const SplitMap smap{{p.taper[0], p.taper[1], p.taper[2], p.taper[3]}, cps < 1 ? 1 : cps};
       timing_begin(TIMING_SYRK, st);
-      contract(Kfu, nchunks, smap, p.nsplit, r0 > 0 ? 1 : 0, w.slab);
+      contract(Kfu, rows / NB, split_map(p.taper, rows / NB, p.nsplit), p.nsplit, r0 > 0 ? 1 : 0, w.slab);
       timing_end(TIMING_SYRK, st);
       cx.syrk_timed_rows = rows;
     }
   }
-  const int nb32 = p.Mp / 32;
-  reduce_phi_kernel<<<nb32 * (nb32 + 1) / 2, 256, 0, st>>>(w.slab, nslabs, p.ntiles, M, sf2 * sf2, Phi);
-  // (the fp64 assembly leaves asm_sub partials per row block, the integer path's assembly one)
-  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(w.bpart, p.Npad / ASM_ROWS * (use_i8 ? 1 : p.asm_sub), p.Mp, BRED_G, w.btmp);
-  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.btmp, BRED_G, p.Mp, M, w.yypart, 256, sf2,
-                                                         sf2 * (double)N, b, yy, kappa);
+  finish_stats(p, w, nslabs, use_i8 ? 1 : p.asm_sub, sf2, N, M, Phi, b, yy, kappa, st);  // (the integer path's assembly: one partial per row block)
   return check_launch();
 }
 
@@ -1109,7 +1096,7 @@ extern "C" int sgp_suffstats_fwd(const double* X, int64_t ldx, const double* y, 
 // T_out (optional, sgp_kfu_len(N, M) doubles): T (unit amplitude, no sf2) is left there for sgp_suffstats_bwd_factored_ex, which then
 // needs neither the assembly nor the product again.
 extern "C" size_t sgp_suffstats_whitened_rows_workspace_bytes(int64_t N, int M, int d, int caller_owns_t) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p = make_stream_plan(N, M, d);
   if (caller_owns_t) p.sc_rows = p.Npad;
   return carve_wh_rows(nullptr, p, caller_owns_t != 0).bytes;
@@ -1119,26 +1106,17 @@ extern "C" int sgp_suffstats_fwd_whitened_rows(const double* X, int64_t ldx, con
                                                const double* kuu_linv, double* W, double* u, double* yy, double* kappa, double* T_out,
                                                void* ws, size_t ws_bytes, sgp_stream_t stream) {
   Ctx& cx = cur_ctx();
-  if (!Z || !inv_ls || !kuu_linv || !W || !u || !yy || !kappa || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id >= SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;  // the composite kernel keeps the chunked routine
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  // (no composite kernel here: it keeps the chunked routine)
+  if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, W, u, yy, kappa}, X, ldx, y, ldz, N, M, d, kernel_id, false)) return bad;
   StreamPlan p = make_stream_plan(N, M, d);
   if (T_out) p.sc_rows = p.Npad;  // the caller keeps all of T: one super-chunk
   WhRowsWs w = carve_wh_rows(ws, p, T_out != nullptr);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-  stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, w.f.Xs, w.f.ys, w.f.Zs, w.f.yypart, st);
+  stream_prologue(p, make_kern_args(inv_ls, sf2, d), X, ldx, y, Z, ldz, N, M, w.f.Xs, w.f.ys, w.f.Zs, w.f.yypart, st);
   transpose_square(kuu_linv, p.Mp, w.R, st);  // R = L^-T as a plain row-major operand
-  if (p.Npad == 0)
-    syrk_tile_kernel<4, false, false><<<p.ntiles * p.nsplit, 256, 0, st>>>(w.f.Kfu, p.Mp, 0, SplitMap{{0, 0, 0, 0}, 1}, p.ntiles, 0, w.f.slab,
-                                                                           p.nsplit);
-  for (int64_t r0 = 0; r0 < p.Npad; r0 += p.sc_rows) {
-    const int64_t rows = (p.Npad - r0) < p.sc_rows ? (p.Npad - r0) : p.sc_rows;
+  if (p.Npad == 0) zero_slabs(p, w.f.Kfu, w.f.slab, st);
+  for (auto [r0, rows] : SuperChunks{p.Npad, p.sc_rows}) {
     double* T = T_out ? T_out + (size_t)r0 * p.Mp : w.T;
     timing_begin(TIMING_ASSEMBLE, st);
     stream_assemble(p, kernel_id, w.f.Xs, w.f.ys, w.f.Zs, r0, rows, N, M, w.f.Kfu, w.f.bpart, st);  // (its K'^T y partials are overwritten below)
@@ -1148,18 +1126,12 @@ extern "C" int sgp_suffstats_fwd_whitened_rows(const double* X, int64_t ldx, con
     g.m = (int)rows; g.n = p.Mp; g.k = p.Mp; g.khi_mask = 2;
     gemm(g, st);
     tpart_kernel<<<dim3((unsigned)(rows / ASM_ROWS), (p.Mp + 255) / 256), 256, 0, st>>>(T, w.f.ys, r0, p.Mp, w.f.bpart);
-    const int64_t nchunks = rows / NB;
-    const int cps = (int)((nchunks + p.nsplit - 1) / p.nsplit);
-    const SplitMap smap{{p.taper[0], p.taper[1], p.taper[2], p.taper[3]}, cps < 1 ? 1 : cps};
     timing_begin(TIMING_SYRK, st);
-    launch_syrk(cx, T, p.Mp, nchunks, smap, p.ntiles, p.nsplit, r0 > 0 ? 1 : 0, w.f.slab, st);
+    launch_syrk(cx, T, p.Mp, rows / NB, split_map(p.taper, rows / NB, p.nsplit), p.ntiles, p.nsplit, r0 > 0 ? 1 : 0, w.f.slab, st);
     timing_end(TIMING_SYRK, st);
     cx.syrk_timed_rows = rows;
   }
-  const int nb32 = p.Mp / 32;
-  reduce_phi_kernel<<<nb32 * (nb32 + 1) / 2, 256, 0, st>>>(w.f.slab, p.nsplit, p.ntiles, M, sf2 * sf2, W);
-  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(w.f.bpart, p.Npad / ASM_ROWS, p.Mp, BRED_G, w.f.btmp);
-  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.f.btmp, BRED_G, p.Mp, M, w.f.yypart, 256, sf2, sf2 * (double)N, u, yy, kappa);
+  finish_stats(p, w.f, p.nsplit, 1, sf2, N, M, W, u, yy, kappa, st);  // (tpart_kernel: one partial per row block)
   return check_launch();
 }
 
@@ -1175,7 +1147,7 @@ extern "C" int sgp_suffstats_fwd_whitened_rows(const double* X, int64_t ldx, con
 // Kfu_out (optional, sgp_kfu_len doubles): the fp64 K'_fu for sgp_suffstats_bwd (explicit Phibar -- good to ~3 x the tolerance only,
 // include/sgp.h).  level 1: 34 digit pairs, 2: 39.
 extern "C" size_t sgp_suffstats_extended_workspace_bytes(int64_t N, int M, int d) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p = make_stream_plan(N, M, d);
   return carve_ext(nullptr, p, p.sc_rows).bytes;
 }
@@ -1202,29 +1174,21 @@ extern "C" int sgp_suffstats_fwd_extended_f16(const double* X, int64_t ldx, cons
                                               const double* kuu_linv, int level, double* W, double* u, double* yy, double* kappa,
                                               double* Kfu_out, uint16_t* Kfu_f16_out, double* phi_diag, void* ws, size_t ws_bytes,
                                               sgp_stream_t stream) {
-  if (Kfu_f16_out && !Kfu_out) return SGP_ERR_ARG;
-  if (!Z || !inv_ls || !kuu_linv || !W || !u || !yy || !kappa || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id >= SGP_KERNEL_COMPOSITE || level < 1 || level > 2) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  if ((Kfu_f16_out && !Kfu_out) || level < 1 || level > 2) return SGP_ERR_ARG;
+  if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, W, u, yy, kappa}, X, ldx, y, ldz, N, M, d, kernel_id, false)) return bad;
   StreamPlan p = make_stream_plan(N, M, d);
   const int64_t qrows = p.sc_rows;
   ExtWs w = carve_ext(ws, p, qrows);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-  stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
+  stream_prologue(p, make_kern_args(inv_ls, sf2, d), X, ldx, y, Z, ldz, N, M, w.Xs, w.ys, w.Zs, w.yypart, st);
   const int ns = i8_nsplit(qrows > 0 ? qrows : 1, p.Mp);
   const size_t nslab = (size_t)ns * p.ntiles * TILE * TILE;
   if (p.Npad == 0) {
     fill_zero(w.slab, nslab, st);
     fill_zero(w.slab_lo, nslab, st);
   }
-  for (int64_t r0 = 0; r0 < p.Npad; r0 += qrows) {
-    const int64_t rows = (p.Npad - r0) < qrows ? (p.Npad - r0) : qrows;
+  for (auto [r0, rows] : SuperChunks{p.Npad, qrows}) {
     timing_begin(TIMING_ASSEMBLE, st);
     i8_assemble(p, kernel_id, w.Xs, w.ys, w.Zs, r0, rows, N, M, w.Q, Kfu_out ? Kfu_out + (size_t)r0 * p.Mp : nullptr, w.bpart, st,
                 Kfu_f16_out ? Kfu_f16_out + (size_t)r0 * p.Mp : nullptr);
@@ -1241,8 +1205,7 @@ extern "C" int sgp_suffstats_fwd_extended_f16(const double* X, int64_t ldx, cons
   if (phi_diag) ext_phi_diag_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.Ph, M, p.Mp, sf2 * sf2, phi_diag);
   // b = K_uf y (fp64, with its amplitude), u = L^-1 b
   fill_zero(w.bpad, p.Mp, st);
-  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(w.bpart, p.Npad / ASM_ROWS, p.Mp, BRED_G, w.btmp);
-  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.btmp, BRED_G, p.Mp, M, w.yypart, 256, sf2, sf2 * (double)N, w.bpad, yy, kappa);
+  finish_b(p, w, 1, sf2, N, M, w.bpad, yy, kappa, st);
   gemv(kuu_linv, p.Mp, p.Mp, false, w.bpad, w.upad, st);
   crop_copy(w.upad, 1, u, 1, M, 1, st);
   return check_launch();

@@ -377,14 +377,7 @@ static void launch_digits(int kid, dim3 grid, hipStream_t st, const double* Xs, 
 template <bool WK>
 static void launch_digits_dp(int DP, int kid, dim3 grid, hipStream_t st, const double* Xs, const double* ys, const double* Zs,
                              int64_t row0, int64_t N, int M, int Mp, uint8_t* Q, double* Kfu, uint16_t* Kh, double* bpart) {
-  switch (DP) {
-    case 2: launch_digits<2, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-    case 4: launch_digits<4, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-    case 8: launch_digits<8, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-    case 16: launch_digits<16, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-    case 24: launch_digits<24, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-    default: launch_digits<32, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); break;
-  }
+  dispatch_dp(DP, [&](auto dp) { launch_digits<decltype(dp)::value, WK>(kid, grid, st, Xs, ys, Zs, row0, N, M, Mp, Q, Kfu, Kh, bpart); });
 }
 
 // Digit planes of rows [row0, row0 + rows) (rows a multiple of ASM_ROWS) into Q (which starts at row0); Kfu (optional, starts at

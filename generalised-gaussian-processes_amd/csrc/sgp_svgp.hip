@@ -364,19 +364,11 @@ static SvgpWs carve_svgp(void* ws, int Mp, int Bp, int M, int d) {
   return w;
 }
 
-static KernArgs make_ka_s(const double* inv_ls, double sf2, int d) {
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = j < d ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-  return ka;
-}
-
 // shared forward: fills w.A, w.T, w.mu, w.v (and L in Kp, L^-1 in Linv, padded m, padded tril(LS))
 static void svgp_forward(const SvgpWs& w, const double* Xb, int64_t ldx, int64_t B, const double* Z, int64_t ldz,
                          const double* inv_ls, double sf2, double jitter, const double* m, const double* LS, int M, int d,
                          int kernel_id, int Mp, int Bp, int* info, hipStream_t st) {
-  const KernArgs ka = make_ka_s(inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   zero_ints(info, 1, st);
   sgp_kuu(Z, ldz, inv_ls, sf2, jitter, M, d, kernel_id, w.Kuu, st);
   pad_copy(w.Kuu, M, M, M, w.Kp, Mp, Mp, Mp, 1.0, st);
@@ -943,7 +935,7 @@ extern "C" int sgp_svgp_elbo(const double* Xb, int64_t ldx, const double* yb, in
   SvgpWs w = carve_svgp(ws, Mp, Bp, M, d);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const KernArgs ka = make_ka_s(inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   static const GHTable gh = make_gh();
   const double invB = 1.0 / (double)B, invN = 1.0 / (double)N_total;
 
@@ -1024,7 +1016,7 @@ static int svgp_batch_impl(int phase, const double* Xb, int64_t ldx, const doubl
   SvgpThetaS th{};
   for (int s = 0; s < S; ++s) {
     if (likelihood_id == 0 && !predict && !(s2[s] > 0.0)) return SGP_ERR_ARG;
-    th.ka[s] = make_ka_s(inv_ls + (size_t)s * d, sf2[s], d);
+    th.ka[s] = make_kern_args(inv_ls + (size_t)s * d, sf2[s], d);
     th.s2[s] = s2[s];
   }
   const int Mp = padded_m(M), Bp = (int)round_up64(B, 64);
@@ -1203,7 +1195,7 @@ static int mixture_predict_impl(const double* X, int64_t ldx, const double* y, i
   SvgpThetaS th{};
   for (int s = 0; s < S; ++s) {
     if (!(s2[s] > 0.0) || !(sf2[s] > 0.0)) return SGP_ERR_ARG;
-    th.ka[s] = make_ka_s(inv_ls + (size_t)s * d, sf2[s], d);
+    th.ka[s] = make_kern_args(inv_ls + (size_t)s * d, sf2[s], d);
     th.s2[s] = s2[s];
   }
   const int Mp = padded_m(M);

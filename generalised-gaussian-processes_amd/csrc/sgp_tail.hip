@@ -12,6 +12,7 @@
 #include "sgp_dense.hpp"
 #include "sgp_ctx.hpp"
 #include "sgp_composite.hpp"
+#include "sgp_stream.hpp"
 
 namespace sgp {
 
@@ -555,13 +556,6 @@ __global__ __launch_bounds__(256) void yy_kappa_kernel(const double* __restrict_
   }
 }
 
-static KernArgs make_ka(const double* inv_ls, double sf2, int d) {
-  KernArgs ka;
-  for (int j = 0; j < SGP_MAX_DIM; ++j) ka.inv_ls[j] = (inv_ls && j < d) ? inv_ls[j] : 0.0;
-  ka.sf2 = sf2;
-  ka.d = d;
-  return ka;
-}
 static int grid_for(int64_t total, int cap = 2048) {
   int64_t g = (total + 255) / 256;
   if (g < 1) g = 1;
@@ -647,7 +641,7 @@ extern "C" int sgp_kuu(const double* Z, int64_t ldz, const double* inv_ls, doubl
     comp_kmatrix(Z, ldz, M, Z, ldz, M, cs, d, M, M, jitter, Kuu, st);
     return check_launch();
   }
-  const KernArgs ka = make_ka(inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   const int g = grid_for((int64_t)M * M);
   switch (kernel_id) {
     case SGP_KERNEL_RBF: kuu_kernel<SGP_KERNEL_RBF><<<g, 256, 0, st>>>(Z, ldz, ka, jitter, M, Kuu); break;
@@ -682,7 +676,7 @@ extern "C" int sgp_kuu_bwd(const double* Z, int64_t ldz, const double* inv_ls, d
   Carver c(ws);
   double* part = c.take<double>((size_t)M * (d + 1));
   double* gzraw = c.take<double>((size_t)M * d);
-  const KernArgs ka = make_ka(inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   if (!g_Z) {  // totals only: a quarter of the launch time (see kuu_bwd_total_kernel)
     const int G = M < 1024 ? M : 1024;
     switch (kernel_id) {
@@ -1135,7 +1129,7 @@ static int wh_slices(int Mp, int64_t Tc) {
   return S;
 }
 extern "C" size_t sgp_suffstats_whitened_workspace_bytes(int64_t N, int M, int d) {
-  if (N < 0 || M <= 0 || d <= 0 || d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return 0;
+  if (!stream_shape_ok(N, M, d)) return 0;
   const size_t Mp = padded_m(M), Tc = (size_t)wh_chunk(N);
   Carver c(nullptr);
   c.take<double>(Mp * Tc);
@@ -1149,10 +1143,7 @@ extern "C" int sgp_suffstats_fwd_whitened(const double* X, int64_t ldx, const do
                                           const double* inv_ls, double sf2, int64_t N, int M, int d, int kernel_id,
                                           const double* kuu_linv, double* W, double* u, double* yy, double* kappa, void* ws,
                                           size_t ws_bytes, sgp_stream_t stream) {
-  if (!Z || !inv_ls || !kuu_linv || !W || !u || !yy || !kappa || N < 0 || M <= 0 || d <= 0 || ldz < d) return SGP_ERR_ARG;
-  if (N > 0 && (!X || !y || ldx < d)) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_COMPOSITE) return SGP_ERR_ARG;
-  if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, W, u, yy, kappa}, X, ldx, y, ldz, N, M, d, kernel_id, true)) return bad;
   CompSpec cs{};
   double kdiag = sf2;
   if (kernel_id == SGP_KERNEL_COMPOSITE) {
@@ -1171,7 +1162,7 @@ extern "C" int sgp_suffstats_fwd_whitened(const double* X, int64_t ldx, const do
   const int S = wh_slices(Mp, Tc);
   double* parts = c.take<double>((size_t)S * Mp * Mp);
   if (S > 1) fill_zero(parts, (size_t)S * Mp * Mp, st);  // the tiles above the diagonal are never written; the reduction reads them
-  const KernArgs ka = make_ka(kernel_id == SGP_KERNEL_COMPOSITE ? nullptr : inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(kernel_id == SGP_KERNEL_COMPOSITE ? nullptr : inv_ls, sf2, d);
   if (N == 0) {
     fill_zero(Wp, (size_t)Mp * Mp, st);
     fill_zero(up, Mp, st);
@@ -1251,7 +1242,7 @@ extern "C" int sgp_predict(const double* Xs, int64_t ldxs, int64_t T, const doub
     AtA = c.take<double>((size_t)Tc * Tc);
     CtC = c.take<double>((size_t)Tc * Tc);
   }
-  const KernArgs ka = make_ka(inv_ls, sf2, d);
+  const KernArgs ka = make_kern_args(inv_ls, sf2, d);
   pad_copy(factors, M, M, M, Li, Mp, Mp, Mp, 1.0, st);
   pad_copy(factors + (size_t)M * M, M, M, M, G, Mp, Mp, Mp, 1.0, st);
   pad_copy(factors + (size_t)2 * M * M, 1, M, 1, q, 1, Mp, 1, 0.0, st);

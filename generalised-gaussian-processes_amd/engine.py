@@ -169,6 +169,26 @@ class HipEngine:
         return torch.empty(*shape, dtype=torch.float64, device=self.device)
 
     # ------------------------------------------------------------------ pass 1
+    def _pass1(self, X, y, Z, kuu_linv, out, ws_name: str, ws_query, *query_args, limits: str = ""):
+        """What the four ``suffstats*`` wrappers share: shapes, tensor checks, the packed ``out``, the workspace (``ws_query`` of this
+        engine's context at (N, M, d, *query_args), cached as ``ws_name``) and the four pointers [Phi or W | b or u | yy | kappa] into
+        ``out``.  Returns (N, M, d, out, ws, pointers)."""
+        N, d = X.shape
+        M = Z.shape[0]
+        self._chk(Z, "Z")
+        if kuu_linv is not None:
+            self._chk(kuu_linv, "kuu_linv")
+        if N > 0:
+            self._chk(X, "X"), self._chk(y, "y")
+        if out is None:
+            out = self.empty(M * M + M + 2)
+        nbytes = ws_query(self._c(), N, M, d, *query_args)
+        if nbytes == 0:
+            raise ValueError("unsupported shape N=%d M=%d d=%d%s" % (N, M, d, limits))
+        base = out.data_ptr()
+        stats = [C.c_void_p(base + 8 * o) for o in (0, M * M, M * M + M, M * M + M + 1)]
+        return N, M, d, out, self._workspace(ws_name, nbytes), stats
+
     def kfu_buffer(self, N: int, M: int) -> torch.Tensor:
         """Caller-owned K'_fu block (see include/sgp.h: sgp_kfu_len) for ``suffstats(..., kfu=)``."""
         return self.empty(self.lib.sgp_kfu_len(N, M))
@@ -183,47 +203,25 @@ class HipEngine:
 
         ``kfu`` (optional, from ``kfu_buffer``) keeps the assembled kernel block for ``suffstats_bwd``.  ``gate``: an event
         already recorded on another stream that the integer-core contraction waits for (include/sgp.h: sgp_set_pass1_gate)."""
-        N, d = X.shape
-        M = Z.shape[0]
-        self._chk(Z, "Z")
-        if N > 0:
-            self._chk(X, "X"), self._chk(y, "y")
-        if out is None:
-            out = self.empty(M * M + M + 2)
         # with a caller-owned K'_fu the library's own super-chunk (up to 16 GiB) is not part of the workspace
-        nbytes = self.lib.sgp_ctx_suffstats_workspace_bytes(self._c(), N, M, d, 1 if kfu is not None else 0)
-        if nbytes == 0:
-            raise ValueError("unsupported shape N=%d M=%d d=%d (d <= %d, M <= %d)" % (N, M, d, _lib.SGP_MAX_DIM, _lib.SGP_MAX_INDUCING))
-        ws = self._workspace("fwd_kfu" if kfu is not None else "fwd", nbytes)
-        base = out.data_ptr()
+        N, M, d, out, ws, stats = self._pass1(X, y, Z, None, out, "fwd_kfu" if kfu is not None else "fwd",
+                                              self.lib.sgp_ctx_suffstats_workspace_bytes, 1 if kfu is not None else 0,
+                                              limits=" (d <= %d, M <= %d)" % (_lib.SGP_MAX_DIM, _lib.SGP_MAX_INDUCING))
         if gate is not None:
             self.lib.sgp_ctx_set_pass1_gate(self._c(), C.c_void_p(gate.cuda_event))
         st = self.lib.sgp_ctx_suffstats_fwd(
             self._c(), self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), N, M, d, _kernel_id(kernel),
-            C.c_void_p(base), C.c_void_p(base + 8 * M * M), C.c_void_p(base + 8 * (M * M + M)),
-            C.c_void_p(base + 8 * (M * M + M + 1)), self._ptr(kfu), self._ptr(ws), ws.numel(), self._stream())
+            *stats, self._ptr(kfu), self._ptr(ws), ws.numel(), self._stream())
         _lib.check("sgp_suffstats_fwd", st)
         return out
 
     def suffstats_whitened(self, X, y, Z, ls, sf2, kuu_linv, kernel="rbf", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Packed local statistics in the whitened basis, [W = A A^T (M*M) | u = A y (M) | yy | kappa] with A = L^-1 K_uf
         (PyMC3's op order; ``kuu_linv`` from ``kuu_factor``).  Same layout and all-reduce as ``suffstats``."""
-        N, d = X.shape
-        M = Z.shape[0]
-        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv")
-        if N > 0:
-            self._chk(X, "X"), self._chk(y, "y")
-        if out is None:
-            out = self.empty(M * M + M + 2)
-        nbytes = self.lib.sgp_ctx_suffstats_whitened_workspace_bytes(self._c(), N, M, d)
-        if nbytes == 0:
-            raise ValueError("unsupported shape N=%d M=%d d=%d" % (N, M, d))
-        ws = self._workspace("fwd_whitened", nbytes)
-        base = out.data_ptr()
+        N, M, d, out, ws, stats = self._pass1(X, y, Z, kuu_linv, out, "fwd_whitened", self.lib.sgp_ctx_suffstats_whitened_workspace_bytes)
         st = self.lib.sgp_ctx_suffstats_fwd_whitened(
             self._c(), self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), N, M, d, _kernel_id(kernel),
-            self._ptr(kuu_linv), C.c_void_p(base), C.c_void_p(base + 8 * M * M), C.c_void_p(base + 8 * (M * M + M)),
-            C.c_void_p(base + 8 * (M * M + M + 1)), self._ptr(ws), ws.numel(), self._stream())
+            self._ptr(kuu_linv), *stats, self._ptr(ws), ws.numel(), self._stream())
         _lib.check("sgp_suffstats_fwd_whitened", st)
         return out
 
@@ -231,27 +229,15 @@ class HipEngine:
                                 t_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``suffstats_whitened`` for a large shard, in the streaming layout (include/sgp.h: sgp_suffstats_fwd_whitened_rows; stationary
         kernels).  ``t_out`` (from ``kfu_buffer``) keeps T = K'_fu L^-T for ``suffstats_bwd_factored(..., t_in=)``."""
-        N, d = X.shape
-        M = Z.shape[0]
-        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv")
-        if N > 0:
-            self._chk(X, "X"), self._chk(y, "y")
-        if out is None:
-            out = self.empty(M * M + M + 2)
+        N, M, d, out, ws, stats = self._pass1(X, y, Z, kuu_linv, out, "fwd_whitened_rows_t" if t_out is not None else "fwd_whitened_rows",
+                                              self.lib.sgp_ctx_suffstats_whitened_rows_workspace_bytes, 1 if t_out is not None else 0)
         if t_out is not None:
             self._chk(t_out, "t_out")
             if t_out.numel() < self.lib.sgp_kfu_len(N, M):
                 raise ValueError("t_out holds %d doubles, sgp_kfu_len(N, M) = %d" % (t_out.numel(), self.lib.sgp_kfu_len(N, M)))
-        nbytes = self.lib.sgp_ctx_suffstats_whitened_rows_workspace_bytes(self._c(), N, M, d, 1 if t_out is not None else 0)
-        if nbytes == 0:
-            raise ValueError("unsupported shape N=%d M=%d d=%d" % (N, M, d))
-        ws = self._workspace("fwd_whitened_rows_t" if t_out is not None else "fwd_whitened_rows", nbytes)
-        base = out.data_ptr()
         st = self.lib.sgp_ctx_suffstats_fwd_whitened_rows(
             self._c(), self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), N, M, d, _kernel_id(kernel),
-            self._ptr(kuu_linv), C.c_void_p(base), C.c_void_p(base + 8 * M * M), C.c_void_p(base + 8 * (M * M + M)),
-            C.c_void_p(base + 8 * (M * M + M + 1)), self._ptr(t_out) if t_out is not None else C.c_void_p(0), self._ptr(ws), ws.numel(),
-            self._stream())
+            self._ptr(kuu_linv), *stats, self._ptr(t_out), self._ptr(ws), ws.numel(), self._stream())
         _lib.check("sgp_suffstats_fwd_whitened_rows", st)
         return out
 
@@ -263,22 +249,11 @@ class HipEngine:
         K'_fu for ``suffstats_bwd``.  ``level`` 1: 34 digit pairs (Phi to 2^-61), 2: 39 pairs (2^-69).  Stationary kernels.
         ``phi_diag`` (M doubles): receives diag(K_uf K_fu) of this shard for ``streaming_error_report`` (ranks add theirs up).
         ``kfu_f16`` (from ``kfu_f16_buffer``, with ``kfu``): receives the fp16 image of K'_fu for ``suffstats_bwd_lo``."""
-        N, d = X.shape
-        M = Z.shape[0]
-        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv")
-        if N > 0:
-            self._chk(X, "X"), self._chk(y, "y")
-        if out is None:
-            out = self.empty(M * M + M + 2)
+        N, M, d, out, ws, stats = self._pass1(X, y, Z, kuu_linv, out, "fwd_extended", self.lib.sgp_ctx_suffstats_extended_workspace_bytes)
         if kfu is not None:
             self._chk(kfu, "kfu")
             if kfu.numel() < self.lib.sgp_kfu_len(N, M):
                 raise ValueError("kfu holds %d doubles, sgp_kfu_len(N, M) = %d" % (kfu.numel(), self.lib.sgp_kfu_len(N, M)))
-        nbytes = self.lib.sgp_ctx_suffstats_extended_workspace_bytes(self._c(), N, M, d)
-        if nbytes == 0:
-            raise ValueError("unsupported shape N=%d M=%d d=%d" % (N, M, d))
-        ws = self._workspace("fwd_extended", nbytes)
-        base = out.data_ptr()
         if phi_diag is not None:
             self._chk(phi_diag, "phi_diag")
             if phi_diag.numel() < M:
@@ -289,10 +264,8 @@ class HipEngine:
                 raise ValueError("kfu_f16: a contiguous float16 tensor of sgp_kfu_len(N, M) elements on this device, together with kfu")
         st = self.lib.sgp_ctx_suffstats_fwd_extended_f16(
             self._c(), self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), N, M, d, _kernel_id(kernel),
-            self._ptr(kuu_linv), int(level), C.c_void_p(base), C.c_void_p(base + 8 * M * M), C.c_void_p(base + 8 * (M * M + M)),
-            C.c_void_p(base + 8 * (M * M + M + 1)), self._ptr(kfu) if kfu is not None else C.c_void_p(0),
-            C.c_void_p(kfu_f16.data_ptr()) if kfu_f16 is not None else C.c_void_p(0),
-            self._ptr(phi_diag) if phi_diag is not None else C.c_void_p(0), self._ptr(ws), ws.numel(), self._stream())
+            self._ptr(kuu_linv), int(level), *stats, self._ptr(kfu), self._ptr(kfu_f16), self._ptr(phi_diag), self._ptr(ws), ws.numel(),
+            self._stream())
         _lib.check("sgp_suffstats_fwd_extended", st)
         return out
 
@@ -304,7 +277,7 @@ class HipEngine:
         hi = self.empty(M, M)
         lo = self.empty(M, M) if want_lo else None
         ws = self._workspace("phibar_dd", self.lib.sgp_phibar_dd_workspace_bytes(M))
-        st = self.lib.sgp_phibar_dd(self._ptr(Cw), self._ptr(kuu_linv), M, float(s2), self._ptr(hi), self._ptr(lo) if want_lo else C.c_void_p(0),
+        st = self.lib.sgp_phibar_dd(self._ptr(Cw), self._ptr(kuu_linv), M, float(s2), self._ptr(hi), self._ptr(lo),
                                     self._ptr(ws), ws.numel(), self._stream())
         _lib.check("sgp_phibar_dd", st)
         return hi, lo
@@ -331,10 +304,9 @@ class HipEngine:
         ws = self._workspace("bwd_lo", self.lib.sgp_suffstats_bwd_lo_workspace_bytes_ex(N, M, d, 1 if kfu_f16 is not None else 0))
         base = grads.data_ptr()
         st = self.lib.sgp_suffstats_bwd_lo_f16(self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2),
-                                               self._ptr(Phibar_lo), self._ptr(kfu) if kfu is not None else C.c_void_p(0),
-                                               C.c_void_p(kfu_f16.data_ptr()) if kfu_f16 is not None else C.c_void_p(0), N, M, d,
-                                               _kernel_id(kernel), C.c_void_p(base), C.c_void_p(base + 8 * nh),
-                                               self._ptr(delta) if delta is not None else C.c_void_p(0), self._ptr(ws), ws.numel(), self._stream())
+                                               self._ptr(Phibar_lo), self._ptr(kfu), self._ptr(kfu_f16), N, M, d, _kernel_id(kernel),
+                                               C.c_void_p(base), C.c_void_p(base + 8 * nh), self._ptr(delta), self._ptr(ws), ws.numel(),
+                                               self._stream())
         _lib.check("sgp_suffstats_bwd_lo", st)
         return grads
 
@@ -418,7 +390,7 @@ class HipEngine:
         (all-reduced) ``phi_diag`` of the extended order with ``stride`` 1, or None (whitened order: the estimate IS the bound)."""
         est = C.c_void_p(result[0].data_ptr() + 8 * (OUT_LEN + 1))
         _lib.check("sgp_streaming_error_report",
-                   self.lib.sgp_streaming_error_report(self._ptr(diag) if diag is not None else C.c_void_p(0), int(stride), self._ptr(trace),
+                   self.lib.sgp_streaming_error_report(self._ptr(diag), int(stride), self._ptr(trace),
                                                        float(sf2), float(s2), int(N), int(M), est, self._stream()))
 
     @staticmethod
@@ -700,7 +672,7 @@ class HipEngine:
         st = self.lib.sgp_ctx_suffstats_bwd_factored(
             self._c(), self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), self._ptr(kuu_linv),
             self._ptr(Cw), float(s2), self._ptr(bbar), float(kappabar), N, M, d, _kernel_id(kernel),
-            self._ptr(t_in) if t_in is not None else C.c_void_p(0), C.c_void_p(base),
+            self._ptr(t_in), C.c_void_p(base),
             C.c_void_p(base + 8 * nh), C.c_void_p(base + 8 * (nh + 1)) if want_gz else C.c_void_p(0), self._ptr(ws), ws.numel(),
             self._stream())
         _lib.check("sgp_suffstats_bwd_factored_ex", st)

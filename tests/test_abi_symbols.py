@@ -72,6 +72,90 @@ def test_bad_arguments_are_rejected_before_any_launch(lib):
     assert lib.sgp_chol_lower(one, 4, 4, one, null, 0, null) == -3
 
 
+STREAM_ENTRY_POINTS = ["sgp_suffstats_fwd", "sgp_suffstats_fwd_whitened_rows", "sgp_suffstats_fwd_extended_f16", "sgp_suffstats_fwd_whitened",
+                       "sgp_suffstats_bwd", "sgp_suffstats_bwd_factored_ex", "sgp_suffstats_bwd_lo_f16"]
+
+
+def stream_call(lib, name, **bad):
+    """One call of a row-streaming entry point that is valid except for `bad` -- and for its workspace: there is none unless `bad`
+    brings one, so a call whose fault went unnoticed would end in SGP_ERR_WORKSPACE, never in a launch.  Pointers are the dummy 8
+    (never dereferenced) or 0; inv = 0 passes NULL for the lengthscales."""
+    a = dict(X=8, ldx=2, y=8, Z=8, ldz=2, inv=1, sf2=1.0, N=10, M=4, d=2, kid=0, out=8, linv=8, bar=8, s2=0.1, level=1, kfu=8, kfu_f16=0, t=0,
+             ws=0, nbytes=0)
+    a.update(bad)
+    p = lambda k: C.c_void_p(a[k])
+    head = [p("X"), a["ldx"], p("y"), p("Z"), a["ldz"], (C.c_double * 2)(1.0, 1.0) if a["inv"] else None, a["sf2"]]
+    shape = [a["N"], a["M"], a["d"], a["kid"]]
+    tail = [p("ws"), a["nbytes"], C.c_void_p(0)]
+    one, null = C.c_void_p(8), C.c_void_p(0)
+    args = {
+        "sgp_suffstats_fwd": head + shape + [p("out"), one, one, one, null] + tail,
+        "sgp_suffstats_fwd_whitened": head + shape + [p("linv"), p("out"), one, one, one] + tail,
+        "sgp_suffstats_fwd_whitened_rows": head + shape + [p("linv"), p("out"), one, one, one, p("t")] + tail,
+        "sgp_suffstats_fwd_extended_f16": head + shape + [p("linv"), a["level"], p("out"), one, one, one, null, p("kfu_f16"), null] + tail,
+        "sgp_suffstats_bwd": head + [p("bar"), one, 0.0, null] + shape + [p("out"), one, null] + tail,
+        "sgp_suffstats_bwd_factored_ex": head + [p("linv"), p("bar"), a["s2"], one, 0.0] + shape + [p("t"), p("out"), one, null] + tail,
+        "sgp_suffstats_bwd_lo_f16": head + [p("bar"), p("kfu"), p("kfu_f16")] + shape + [p("out"), one, null] + tail,
+    }[name]
+    return getattr(lib, name)(*args)
+
+
+# The status of every kind of bad call, as the library answered before the seven entry points shared one host-side frame: a NULL
+# required pointer, ldx / ldz < d, a kernel id out of range, the composite id where it is not taken, d = 40, M = 4097, no / a short / a
+# NULL workspace, and calls that are wrong in two ways at once (SGP_ERR_ARG = -1 before SGP_ERR_DIM = -2 before SGP_ERR_WORKSPACE = -3,
+# the checks only one entry point has included).  An empty dict() is the valid call without a workspace.  The first table holds for all
+# seven, the second has what only one of them checks (N = 0 is left out where that path launches).
+STREAM_COMMON_ROWS = [
+    (dict(Z=0), -1), (dict(out=0), -1), (dict(inv=0), -1),
+    (dict(X=0), -1), (dict(ldx=1), -1), (dict(ldz=1), -1),
+    (dict(kid=-1), -1), (dict(kid=4), -1), (dict(d=40, ldx=40, ldz=40), -2),
+    (dict(M=4097), -2), (dict(N=-1), -1), (dict(), -3),
+    (dict(ws=8, nbytes=1), -3), (dict(ws=0, nbytes=1 << 40), -3), (dict(kid=4, M=4097), -1),
+    (dict(Z=0, d=40, ldx=40, ldz=40), -1), (dict(ldx=1, ws=8, nbytes=1), -1), (dict(d=40, ldx=40, ldz=40, ws=8, nbytes=1), -2),
+    (dict(M=4097, ws=0, nbytes=1 << 40), -2),
+]
+STREAM_OWN_ROWS = {
+    "sgp_suffstats_fwd": [(dict(N=0, X=0, y=0), -3)],
+    "sgp_suffstats_fwd_whitened_rows": [(dict(linv=0), -1), (dict(kid=3), -1), (dict(kid=3, d=40, ldx=40, ldz=40), -1)],
+    "sgp_suffstats_fwd_extended_f16": [
+        (dict(linv=0), -1), (dict(kid=3), -1), (dict(kid=3, M=4097), -1),
+        (dict(level=0), -1), (dict(level=3, d=40, ldx=40, ldz=40), -1), (dict(kfu_f16=8), -1),
+        (dict(kfu_f16=8, M=4097), -1), (dict(level=3), -1),
+    ],
+    "sgp_suffstats_fwd_whitened": [(dict(linv=0), -1)],
+    "sgp_suffstats_bwd": [(dict(bar=0), -1)],
+    "sgp_suffstats_bwd_factored_ex": [
+        (dict(linv=0), -1), (dict(s2=0.0), -1), (dict(s2=-1.0, d=40, ldx=40, ldz=40), -1),
+        (dict(t=8, kid=3), -1), (dict(t=8, kid=3, M=4097), -1),
+    ],
+    "sgp_suffstats_bwd_lo_f16": [
+        (dict(kfu=0), -1), (dict(kfu=0, kfu_f16=8), -3), (dict(kid=1), -1),
+        (dict(kid=3), -1), (dict(kid=1, d=40, ldx=40, ldz=40), -1), (dict(kfu=0, M=4097), -1),
+        (dict(kid=2), -1),
+    ],
+}
+
+
+@pytest.mark.parametrize("name", STREAM_ENTRY_POINTS)
+def test_streaming_entry_points_keep_their_status_codes(lib, name):
+    for bad, want in STREAM_COMMON_ROWS + STREAM_OWN_ROWS[name]:
+        assert want < 0  # (a call that is expected to succeed would launch on the dummy pointers)
+        assert stream_call(lib, name, **bad) == want, (name, bad)
+
+
+def test_streaming_workspace_queries_refuse_the_same_shapes(lib):
+    queries = [lib.sgp_suffstats_workspace_bytes, lambda N, M, d: lib.sgp_suffstats_workspace_bytes_ex(N, M, d, 1),
+               lib.sgp_suffstats_whitened_workspace_bytes, lambda N, M, d: lib.sgp_suffstats_whitened_rows_workspace_bytes(N, M, d, 0),
+               lib.sgp_suffstats_extended_workspace_bytes, lib.sgp_suffstats_bwd_workspace_bytes,
+               lambda N, M, d: lib.sgp_suffstats_bwd_workspace_bytes_ex(N, M, d, 1), lib.sgp_suffstats_bwd_factored_workspace_bytes,
+               lambda N, M, d: lib.sgp_suffstats_bwd_factored_workspace_bytes_ex(N, M, d, 1), lib.sgp_suffstats_bwd_lo_workspace_bytes,
+               lambda N, M, d: lib.sgp_suffstats_bwd_lo_workspace_bytes_ex(N, M, d, 1)]
+    for q in queries:
+        assert q(10, 4, 2) > 0 and q(0, 4, 2) > 0 and q(10, 4096, 32) > 0
+        for N, M, d in [(-1, 4, 2), (10, 0, 2), (10, 4, 0), (10, 4, 33), (10, 4097, 2)]:
+            assert q(N, M, d) == 0
+
+
 def test_contexts_carry_their_own_options_and_the_setters_are_shims_over_the_default_one(lib):
     """ABI version 2 (include/sgp.h: sgp_ctx_*): no kernel is launched -- options, the contraction rule, the workspace query."""
     import ggp_amd._lib as L
