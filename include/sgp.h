@@ -576,7 +576,9 @@ int sgp_small_nuts_composite(const double* X, int64_t ldx, const double* y, cons
 /* ---- streaming pass 2: gradients through Kuf -------------------------------------------------------
  * Kbar_uf = 2 Phibar Kuf + bbar y^T is formed tile by tile and contracted with dKuf/d(.) on the fly.
  * Writes (overwrites) g_ls[d] = dF/d lengthscale_j, g_sf2[1] = dF/d sf2 (including the kappa term
- * kappabar * N), g_Z[M*d] (ld d; skipped when g_Z == NULL).  Local shard only; caller all-reduces.  */
+ * kappabar * N), g_Z[M*d] (ld d; skipped when g_Z == NULL).  Local shard only; caller all-reduces.
+ * Phibar (M x M, ld M) need NOT be symmetric: it enters as (Phibar + Phibar^T) / 2, so what is contracted is
+ * Kbar_uf = (Phibar + Phibar^T) Kuf + bbar y^T -- the gradient of sum(Phibar o (Kuf Kuf^T)) + bbar^T Kuf y + kappabar N sf2.  */
 size_t sgp_suffstats_bwd_workspace_bytes(int64_t N, int M, int d);
 size_t sgp_suffstats_bwd_workspace_bytes_ex(int64_t N, int M, int d, int caller_owns_kfu); /* with Kfu_in from pass 1 */
 int sgp_suffstats_bwd(const double* X, int64_t ldx, const double* y,

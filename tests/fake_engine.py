@@ -147,7 +147,7 @@ class OracleEngine:
             Xc = X[s:s + 4096]
             r2 = O.sqdist(Z, Xc, lst)
             K = O.kernel_from_r2(r2, float(sf2), kid)
-            Kbar = 2.0 * Phibar @ K + torch.outer(bbar, y[s:s + 4096])
+            Kbar = (Phibar + Phibar.T) @ K + torch.outer(bbar, y[s:s + 4096])   # (as the library: Phibar enters symmetrised)
             g_sf2 = g_sf2 + (Kbar * K).sum() / sf2
             E = Kbar * O._dk_factors(r2, K, float(sf2), kid)
             diff = Zs[:, None, :] - (Xc / lst)[None, :, :]

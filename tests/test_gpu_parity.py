@@ -682,7 +682,10 @@ def test_integration_md_ctypes_stub_runs(engine):
                                   "SGP_SYRK_NSPLIT=24", "SGP_KBAR_NSPLIT=40", "SGP_KBAR_TAPER=0"])
 def test_tuning_knobs_do_not_change_results(engine, knob):
     """The A/B knobs of the pass-1 contraction (LDS-DMA staging, 8-wave workgroups, full diagonal tiles, fewer splits) are
-    read once per process, so each runs in a child process; all must reproduce the golden sufficient statistics."""
+    read once per process, so each runs in a child process; all must reproduce the golden sufficient statistics.  The two
+    SGP_KBAR_* knobs belong to pass 2: every child also runs suffstats_bwd on the fixture with a fixed random (non-symmetric) Phibar
+    and bbar, against the oracle engine's float64 restatement -- component-wise within 1e-12 of the condition scale A of
+    tests/pass2_reference.py (the oracle engine itself stays within 2e-16 A of the long-double reference)."""
     import subprocess
     import sys as _sys
     code = (
@@ -693,6 +696,14 @@ def test_tuning_knobs_do_not_change_results(engine, knob):
         "M = G['Z'].shape[0]; Phi = full[:M*M].reshape(M, M)\n"
         "assert np.abs(Phi - G['Phi']).max() < 1e-12 * np.abs(G['Phi']).max(), np.abs(Phi - G['Phi']).max()\n"
         "assert np.abs(full[M*M:M*M+M] - G['b']).max() < 1e-12 * np.abs(G['b']).max()\n"
+        "import pass2_reference as R; from fake_engine import OracleEngine\n"
+        "g = torch.Generator().manual_seed(17); Pb = torch.randn(M, M, dtype=torch.float64, generator=g)\n"
+        "bb = torch.randn(M, dtype=torch.float64, generator=g)\n"
+        "X, y, Z = (torch.as_tensor(np.ascontiguousarray(G[k]), dtype=torch.float64) for k in 'XyZ'); ls, sf2 = G['ls'].tolist(), float(G['sf2'])\n"
+        "got = eng.suffstats_bwd(dev(X, eng), dev(y, eng), dev(Z, eng), ls, sf2, dev(Pb, eng), dev(bb, eng), -0.7, 'rbf', want_gz=True).cpu()\n"
+        "ref = OracleEngine().suffstats_bwd(X, y, Z, ls, sf2, Pb, bb, -0.7, 'rbf', want_gz=True)\n"
+        "A = R.pack(R.bwd_reference(X, y, Z, ls, sf2, Pb, bb, -0.7, 'rbf')[1], True)\n"
+        "w = R.worst_ratio(got, ref.numpy().astype(R.LD), A); print('pass 2: worst err / A = %%.3e' %% w); assert w <= 1e-12, w\n"
         "print('ok')\n" % (ROOT, os.path.join(ROOT, "tests")))
     env = dict(os.environ)
     k, v = knob.split("=")
