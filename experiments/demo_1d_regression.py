@@ -3,8 +3,9 @@
 
 Same data recipe (seeded torch RNG, train on |x| > 2, test grid linspace(-8, 8, 1000), Z_init = randn(25)),
 same two models (SparseGPR with 2000 Adam steps at lr 0.01; BayesianSparseGPR_HMC with the
-[100, 200, 500, 1000, 1500, 1999] HMC schedule), same metrics.  The GPflow "JointHMC" third panel and the
-plots are out of scope.  Prints one JSON object (keys follow experiments/regression.py:157-179).
+[100, 200, 500, 1000, 1500, 1999] HMC schedule), same metrics.  The GPflow "JointHMC" third panel (:145-164: SGPMC + HMC, 500 burn-in
+transitions and 500 draws) is added to the JSON object by ``--joint_hmc`` (off by default: without the flag the output is unchanged);
+the plots are out of scope.  Prints one JSON object (keys follow experiments/regression.py:157-179).
 """
 import argparse
 import json
@@ -30,6 +31,9 @@ def main():
     ap.add_argument("--max_iters", type=int, default=2000)
     ap.add_argument("--num_inducing", type=int, default=25)
     ap.add_argument("--skip_hmc", action="store_true")
+    ap.add_argument("--joint_hmc", action="store_true", help="also the third panel: SGPMC + HMC (train_sgp_hmc / predict_sgpmc)")
+    ap.add_argument("--joint_tune", type=int, default=500)
+    ap.add_argument("--joint_samples", type=int, default=500)
     args = ap.parse_args()
 
     torch.manual_seed(45)
@@ -72,6 +76,20 @@ def main():
             perf_times=perf, step_sizes=step_sizes, num_inducing=args.num_inducing, max_iter=args.max_iters, n_mixture=len(preds),
             ls_mean=float(np.mean(trace["ls"])), sig_n_mean=float(np.mean(trace["sig_n"])),
             leapfrogs_last_phase=int(trace.n_leapfrog), sampler_on_device=bool(getattr(trace, "device_resident", False)))
+    if args.joint_hmc:
+        # demo_1d_regression.py:160-164,213-217 of the reference; the mixture NLPD is the metric its SGPMC driver reports (models/sgp_hmc.py:154)
+        t0 = time.time()
+        jm, jtrace, sample_secs = ggp_amd.train_sgp_hmc((X_train, Y_train[:, None]), Z_init[:, None], 1, args.joint_tune, args.joint_samples, seed=45)
+        wall = time.time() - t0
+        pred_mean, f_means, y_stds = ggp_amd.predict_sgpmc(jm, jtrace, X_test[:, None])
+        lower, upper = ggp_amd.get_posterior_predictive_uncertainty_intervals(f_means, y_stds)
+        out["JointHMC"] = ggp_amd.experiment_tools.result_record(
+            "demo_1d", "JointHMC", float(rmse(torch.as_tensor(pred_mean), Y_test, ystd)),
+            float(ggp_amd.negative_log_predictive_mixture_density(Y_test, f_means, y_stds, 1.0)), wall, sampling_secs=sample_secs,
+            num_inducing=args.num_inducing, tune=args.joint_tune, num_samples=args.joint_samples, n_mixture=int(f_means.shape[0]),
+            acceptance=float(np.mean(jtrace.get_sampler_stats("is_accepted"))), step_size=float(jtrace.get_sampler_stats("step_size")[-1]),
+            warmup=jm.warmup, lengthscale_mean=float(np.mean(jtrace["lengthscales"])), noise_variance_mean=float(np.mean(jtrace["noise_variance"])),
+            coverage_95=float(np.mean((Y_test.numpy() >= lower) & (Y_test.numpy() <= upper))))
     print(json.dumps(out))
 
 

@@ -10,11 +10,12 @@ from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, sha
 from . import datasets, experiment_tools  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
                       MultivariateNormal, RBFKernel, ScaleKernel, ZeroMean, settings)
-from .hmc import NUTS, SplitMix, Trace, sample_nuts, sample_nuts_device  # noqa: F401
-from .metrics import nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
+from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_device  # noqa: F401
+from .metrics import negative_log_predictive_mixture_density, nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
-from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget  # noqa: F401
+from .sgp_hmc import SgpmcModel, get_posterior_predictive_uncertainty_intervals, predict_sgpmc, train_sgp_hmc  # noqa: F401
+from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must work without a GPU (build / symbol checks)

@@ -126,6 +126,16 @@ class GuardState:
             self.open = not (self.predicted < 0.5 * tol)
 
 
+WHITENED_ROWS_MIN_WORK = 1 << 26
+
+
+def whitened_rows_layout(engine, kernel, n_rows, M, min_work=WHITENED_ROWS_MIN_WORK):
+    """The whitened pass 1 of a shard of ``n_rows`` rows runs in the streaming layout (``engine.suffstats_whitened_rows``: stationary
+    kernels, from ``min_work`` local rows x inducing points) instead of through the chunked routine -- the one rule ``CollapsedBound``
+    and ``targets.SgpmcTarget`` share."""
+    return hasattr(engine, "suffstats_whitened_rows") and kernel != "composite" and int(n_rows) * int(M) >= min_work
+
+
 def _world(group):
     if dist is None or not dist.is_available() or not dist.is_initialized():
         return 1
@@ -191,7 +201,7 @@ class CollapsedBound:
         self._kfu_f16 = None
         self.kfu_budget_bytes = 64 << 30
         # local rows x inducing points from which the whitened order runs in the streaming layout (engine.suffstats_whitened_rows)
-        self.whitened_rows_min_work = 1 << 26
+        self.whitened_rows_min_work = WHITENED_ROWS_MIN_WORK
         self.factored_adjoint = True  # whitened order: pass 2 from L^-T Cw L^-1 applied factor by factor (sgp_suffstats_bwd_factored)
         self.fused = True          # single-launch path for small problems (M <= 128, one rank): sgp_small_eval
         self._small = None         # (pinned host theta, device theta, result buffer) of the single-launch path
@@ -474,8 +484,7 @@ class CollapsedBound:
             # with adjoints: also the whitened core Cw of Phibar, so that pass 2 applies L^-T Cw L^-1 factor by factor
             factored = with_adjoints and self.factored_adjoint and hasattr(e, "suffstats_bwd_factored")
             t_keep = None
-            if (hasattr(e, "suffstats_whitened_rows") and self.kernel != "composite"
-                    and int(self.X.shape[0]) * M >= self.whitened_rows_min_work):
+            if whitened_rows_layout(e, self.kernel, int(self.X.shape[0]), M, self.whitened_rows_min_work):
                 # a large shard (the streaming guard's repeats at 10^6 rows): the streaming layout; T = K'_fu L^-T stays for pass 2
                 t_keep = self._kfu_for(M) if factored else None
                 packed = e.suffstats_whitened_rows(self.X, self.y, Z, ls, sf2, linv, self.kernel, t_out=t_keep)

@@ -445,6 +445,36 @@ class HipEngine:
             _lib.check("sgp_bound_from_stats", self.lib.sgp_ctx_bound_from_stats(self._c(), self._ptr(Kuu), *stats, *tail))
         return res
 
+    def sgpmc_tail(self, packed_whitened, v, s2, N, kuu_linv, with_adjoints=False, result=None, vbar_out=None):
+        """The SGPMC tail (include/sgp.h: sgp_sgpmc_from_whitened_stats) on packed whitened statistics [W | u | yy | kappa] and the
+        whitened inducing values ``v`` (M doubles on the device).
+
+        Returns dict(out = [F | data term | prior-of-v term | s2bar | kappabar] in the head of ``buf``, info, buf, and with the adjoints
+        vbar, Cw, bbar, Kuubar).  ``result``: the ``result_buffer`` whose status word ``kuu_factor`` wrote -- the tail factors nothing
+        and that word is the evaluation's status.  ``vbar_out`` (M doubles, e.g. a slice of the result buffer's extras): where
+        vbar is written, so that it comes back with the evaluation's one host copy.  Nothing is synchronised."""
+        M = int(v.numel())
+        self._chk(packed_whitened, "packed_whitened"), self._chk(v, "v")
+        if packed_whitened.numel() < M * M + M + 2:
+            raise ValueError("packed_whitened holds %d doubles, M * M + M + 2 = %d" % (packed_whitened.numel(), M * M + M + 2))
+        buf, out, info = result if result is not None else self.result_buffer()
+        res = {"out": out, "info": info, "buf": buf}
+        vbar = Cw = bbar = Kuubar = None
+        if with_adjoints:
+            if kuu_linv is None:
+                raise ValueError("sgpmc_tail(with_adjoints=True) needs kuu_linv")
+            self._chk(kuu_linv, "kuu_linv")
+            vbar, Cw, bbar, Kuubar = vbar_out if vbar_out is not None else self.empty(M), self.empty(M, M), self.empty(M), self.empty(M, M)
+            res.update(vbar=vbar, Cw=Cw, bbar=bbar, Kuubar=Kuubar)
+        ws = self._workspace("sgpmc", self.lib.sgp_sgpmc_workspace_bytes(M))
+        base = packed_whitened.data_ptr()
+        st = self.lib.sgp_sgpmc_from_whitened_stats(
+            C.c_void_p(base), C.c_void_p(base + 8 * M * M), C.c_void_p(base + 8 * (M * M + M)), C.c_void_p(base + 8 * (M * M + M + 1)),
+            self._ptr(v), float(s2), int(N), M, 1 if with_adjoints else 0, self._ptr(out), self._ptr(vbar), self._ptr(Cw),
+            self._ptr(bbar), self._ptr(Kuubar), self._ptr(kuu_linv), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_from_whitened_stats", st)
+        return res
+
     # ------------------------------------------------------------------ single-launch path for small problems
     def small_supported(self, N: int, M: int, d: int, kernel="rbf") -> bool:
         return bool(self._cf.sgp_small_supported(int(N), int(M), int(d), _kernel_id(kernel)))

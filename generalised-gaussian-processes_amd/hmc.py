@@ -461,3 +461,73 @@ def sample_nuts(target, n_samples: int, tune: int, seed: Optional[int] = None, s
     tr = Trace(samples, stats)
     tr.n_leapfrog = nuts.n_leapfrog
     return tr
+
+
+# ---------------------------------------------------------------------------------------------
+# fixed-length HMC with TFP's simple step-size adaptation (reference models/sgp_hmc.py:67-83)
+# ---------------------------------------------------------------------------------------------
+@few_host_threads
+def sample_hmc(target, n_samples: int, tune: int, seed: Optional[int] = None, start: Optional[Sequence[float]] = None,
+               num_leapfrog_steps=10, step_size=0.01, num_adaptation_steps=10, target_accept=0.8, adaptation_rate=0.1) -> Trace:
+    """``tfp.mcmc.sample_chain(num_results=n_samples, num_burnin_steps=tune, kernel=SimpleStepSizeAdaptation(HamiltonianMonteCarlo(...)))``
+    for a target with ``ndim``, ``logp_and_grad`` and ``constrain`` (``targets.SgpmcTarget``): ``num_leapfrog_steps`` leapfrog steps
+    with an identity mass matrix, then a Metropolis test on the energy difference; a non-finite energy is a rejection.  During the
+    first ``num_adaptation_steps`` transitions the step is multiplied by 1 + ``adaptation_rate`` after a transition whose
+    min(0, log accept ratio) is above log ``target_accept`` and divided by it otherwise; afterwards it is frozen.  [UPSTREAM] that is
+    TFP's published rule as recalled (models/sgp_hmc.py:67-73 sets 10 leapfrog steps, step 0.01, 10 adaptation steps, 0.8, 0.1): TFP is
+    not installed here and nothing was checked against it; chains are comparable statistically, not draw for draw.
+
+    Returns the post-burn-in draws as a ``Trace`` with the target's constrained variables (``variance``, ``lengthscales``,
+    ``noise_variance``, ``V`` for ``SgpmcTarget``) plus ``theta_unc``, and the stats ``is_accepted``, ``log_accept_ratio``,
+    ``step_size`` (the step the transition used), ``perf_counter_diff``.  Random numbers: ``SplitMix(seed)`` -- same seed, same chain."""
+    nd = target.ndim
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0] >> 1)
+    rng = SplitMix(seed)
+
+    def evaluate(q):
+        lp, g = target.logp_and_grad(q)[:2]
+        return float(lp), np.asarray(g, dtype=np.float64)
+
+    q, (lp, g) = _find_start(target, evaluate, rng, start)
+    eps = float(step_size)
+    log_target = math.log(target_accept)
+    samples, rows = [], []
+    n_leapfrog = 0
+    for it in range(tune + n_samples):
+        t0 = time.perf_counter()
+        p0 = rng.standard_normal(nd)
+        h0 = -lp + 0.5 * float(p0 @ p0)
+        qn, lpn, gn = q, lp, g
+        p = p0 + 0.5 * eps * g
+        for step in range(num_leapfrog_steps):
+            qn = qn + eps * p
+            lpn, gn = evaluate(qn)
+            n_leapfrog += 1
+            if not math.isfinite(lpn):
+                break
+            p = p + (eps if step + 1 < num_leapfrog_steps else 0.5 * eps) * gn
+        h1 = -lpn + 0.5 * float(p @ p) if math.isfinite(lpn) else math.inf
+        log_ratio = h0 - h1 if math.isfinite(h1) else -math.inf
+        if math.isnan(log_ratio):
+            log_ratio = -math.inf
+        u = rng.random()
+        accepted = bool(math.log(u) < log_ratio) if u > 0.0 else True
+        if accepted:
+            q, lp, g = qn, lpn, gn
+        used = eps
+        if it < num_adaptation_steps:
+            eps = eps * (1.0 + adaptation_rate) if min(0.0, log_ratio) > log_target else eps / (1.0 + adaptation_rate)
+        if it >= tune:
+            row = dict(target.constrain(q))
+            row["theta_unc"] = np.array(q, dtype=np.float64)
+            samples.append(row)
+            rows.append((accepted, log_ratio, used, time.perf_counter() - t0))
+    stats = {"is_accepted": np.array([r[0] for r in rows], dtype=bool), "log_accept_ratio": np.array([r[1] for r in rows], dtype=np.float64),
+             "step_size": np.array([r[2] for r in rows], dtype=np.float64),
+             "perf_counter_diff": np.array([r[3] for r in rows], dtype=np.float64)}
+    varnames = [k for k in (samples[0] if samples else {}) if k != "theta_unc"]
+    tr = Trace(samples, stats, varnames=varnames or ("variance", "lengthscales", "noise_variance", "V"))
+    tr.n_leapfrog = n_leapfrog
+    tr.final_step_size = eps
+    return tr

@@ -35,3 +35,16 @@ def nlpd_marginal(Y_test_pred, Y_test, Y_std):
 def nlpd_mixture(Y_test_pred_list, Y_test, Y_std):
     """Mean over the per-sample joint nlpd (utils/metrics.py:61-67)."""
     return float(np.mean([float(nlpd(p, Y_test, Y_std)) for p in Y_test_pred_list]))
+
+
+def negative_log_predictive_mixture_density(Y_test, y_mix_loc, y_mix_std, Y_std):
+    """The metric the reference's SGPMC driver reports (utils/metrics.py:70-78, called at models/sgp_hmc.py:154).  ``y_mix_loc`` /
+    ``y_mix_std`` are (components x test points).  As in the reference it is the MEAN OVER COMPONENTS OF THE LOG-densities per test
+    point (not the log of the mean density), minus log ``Y_std``, averaged over the test points, rounded to three decimals and negated."""
+    y = np.asarray(torch.as_tensor(Y_test).detach().to("cpu", torch.float64)).reshape(-1)
+    loc = np.asarray(y_mix_loc, dtype=np.float64)
+    std = np.asarray(y_mix_std, dtype=np.float64)
+    if loc.shape != std.shape or loc.ndim != 2 or loc.shape[1] != y.shape[0]:
+        raise ValueError("y_mix_loc / y_mix_std must both be (components, %d), got %s and %s" % (y.shape[0], loc.shape, std.shape))
+    lp = -0.5 * np.log(2.0 * np.pi * std ** 2) - 0.5 * ((y[None, :] - loc) / std) ** 2 - math.log(_std(Y_std))
+    return float(-np.round(np.mean(np.mean(lp, axis=0)), 3))

@@ -1,0 +1,136 @@
+"""SGPMC + HMC ("JointHMC"): the third sampler row of the reference's tables (models/sgp_hmc.py; Hensman et al. 2015).
+
+GPflow's ``SGPMC`` with a Gaussian likelihood, sampled jointly over the hyper-parameters and the whitened inducing values by
+fixed-length HMC with TFP's simple step-size adaptation.  Here the density is ``targets.SgpmcTarget`` (the whitened sufficient
+statistics streamed by pass 1, the SGPMC tail of include/sgp.h, the factored pass 2) and the sampler ``hmc.sample_hmc``.
+
+The reference's ``train_sgp_hmc`` returns ``(model, hmc_helper, samples, wall_clock_secs)`` and its callers unpack that tuple
+inconsistently; ``hmc_helper`` (GPflow's ``SamplingHelper``) has no counterpart here.  The signatures chosen:
+``train_sgp_hmc(...) -> (model, trace, wall_clock_secs)`` and ``predict_sgpmc(model, trace, X_test) -> (pred_mean, f_means, y_stds)``.
+"""
+from __future__ import annotations
+
+import math
+import time
+
+import numpy as np
+import torch
+
+from .hmc import sample_hmc
+from .targets import SgpmcTarget
+
+
+class SgpmcModel:
+    """What ``train_sgp_hmc`` returns as ``model``: the target (data, kernel, jitter, engine), the inducing inputs the warm-up left
+    (``Z``, frozen during sampling) and the warm-up's record."""
+
+    def __init__(self, target: SgpmcTarget):
+        self.target = target
+        self.engine = target.engine
+        self.kernel = target.kernel
+        self.jitter = target.jitter
+        self.warmup = {}
+
+    @property
+    def Z(self):
+        return self.target.Z
+
+
+def _as_tensor(a):
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+    return t.to(torch.float64)
+
+
+def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed=None, warmup_iters=100):
+    """models/sgp_hmc.py:32-91.  ``data`` = (X_train, Y_train); returns ``(model, trace, wall_clock_secs)``.
+
+    As the reference: (1) a warm-up, ``scipy.optimize.minimize(method="L-BFGS-B", jac=True, maxiter=warmup_iters)`` on -logp over
+    every variable INCLUDING the inducing inputs (:54-55; gpflow.optimizers.Scipy's default method); (2) Z is frozen (:56); (3)
+    ``sample_hmc`` with ``tune`` burn-in transitions and ``num_samples`` draws from where the warm-up ended (:67-83: 10 leapfrog
+    steps, step 0.01, 10 adaptation steps, target 0.8, rate 0.1).  ``wall_clock_secs`` times the sampling only (:86-88)."""
+    from scipy.optimize import minimize
+    X, Y = _as_tensor(data[0]), _as_tensor(data[1]).reshape(-1)
+    if X.dim() == 1:
+        X = X[:, None]
+    Z0 = _as_tensor(Z_init)
+    if Z0.dim() == 1:
+        Z0 = Z0[:, None]
+    if X.shape[1] != int(input_dims) or Z0.shape[1] != int(input_dims):
+        raise ValueError("input_dims = %d, X has %d columns, Z_init has %d" % (int(input_dims), X.shape[1], Z0.shape[1]))
+    target = SgpmcTarget(X, Y, Z0, kernel="rbf", jitter=1e-5, engine=engine)   # SquaredExponential, jitter 1e-5 (:20, :36)
+    model = SgpmcModel(target)
+    M, d, nd = target.M, target.d, target.ndim
+    dev = target.engine.device
+
+    def loss(w):
+        target.set_Z(torch.from_numpy(w[nd:].reshape(M, d).copy()).to(dev))
+        lp, g, gz = target.logp_and_grad(w[:nd], want_gz=True)
+        if not math.isfinite(lp):
+            return 1e100, np.zeros_like(w)
+        return -lp, -np.concatenate([np.asarray(g, dtype=np.float64), gz.detach().to("cpu").numpy().reshape(-1)])
+
+    w0 = np.concatenate([np.asarray(target.start(), dtype=np.float64), Z0.detach().to("cpu").numpy().reshape(-1)])
+    f0 = loss(w0)[0]
+    if int(warmup_iters) > 0:
+        r = minimize(loss, w0, jac=True, method="L-BFGS-B", options={"maxiter": int(warmup_iters)})
+        w1, f1, nit = (r.x, float(r.fun), int(r.nit)) if r.fun <= f0 else (w0, f0, 0)
+    else:
+        w1, f1, nit = w0, f0, 0
+    target.set_Z(torch.from_numpy(w1[nd:].reshape(M, d).copy()).to(dev))   # frozen from here on
+    model.warmup = {"loss_start": float(f0), "loss_end": float(f1), "iterations": nit}
+    t0 = time.time()
+    trace = sample_hmc(target, int(num_samples), int(tune), seed=seed, start=w1[:nd])
+    wall_clock_secs = time.time() - t0
+    return model, trace, wall_clock_secs
+
+
+def predict_sgpmc(model, trace, X_test, n_draws=50):
+    """models/sgp_hmc.py:93-130: ``(pred_mean, f_means, y_stds)``, the last two (draws x test points).  The reference predicts from
+    the FIRST 50 draws of the chain; ``n_draws`` keeps that default (fewer when the trace is shorter).  Per draw ``predict_f`` is the
+    whitened SVGP predictive with q(v) a point mass, ``engine.svgp_predict(m=v, LS=0)``: mean = a^T v, var = k** - |a|^2 with
+    a = L^-1 k_u*; y_std = sqrt(var + noise variance)."""
+    e = model.engine
+    Xs = _as_tensor(X_test)
+    if Xs.dim() == 1:
+        Xs = Xs[:, None]
+    Xs = Xs.to(e.device).contiguous()
+    Z = model.Z
+    M = int(Z.shape[0])
+    n = min(int(n_draws), len(trace))
+    if n <= 0:
+        raise ValueError("the trace holds no draws")
+    LS = torch.zeros(M, M, dtype=torch.float64, device=e.device)
+    f_means, y_stds = [], []
+    for i in range(n):
+        row = trace[i]
+        m = torch.as_tensor(np.asarray(row["V"], dtype=np.float64)).to(e.device).contiguous()
+        mean, var, _ = e.svgp_predict(Xs, Z, [float(t) for t in np.asarray(row["lengthscales"]).reshape(-1)], float(row["variance"]), m, LS,
+                                      jitter=model.jitter, kernel=model.kernel)
+        f_means.append(mean.detach().to("cpu").numpy())
+        y_stds.append(np.sqrt(np.maximum(var.detach().to("cpu").numpy(), 0.0) + float(row["noise_variance"])))
+    f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
+    return np.mean(f_means, axis=0), f_means, y_stds
+
+
+def get_posterior_predictive_uncertainty_intervals(sample_means, sample_stds):
+    """utils/posterior_predictive.py:30-46: the 2.5 % and 97.5 % points of the equal-weight Gaussian mixture of the draws' predictive
+    densities, per test point; inputs (draws x test points), returns (lower, upper).  The reference estimates them from 1000 random
+    mixture draws; here the mixture CDF mean_j Phi((x - mu_j) / sd_j) is solved by bisection, which is deterministic."""
+    mu = np.asarray(sample_means, dtype=np.float64)
+    sd = np.asarray(sample_stds, dtype=np.float64)
+    if mu.ndim == 1:
+        mu, sd = mu[:, None], sd[:, None]
+    erf = np.vectorize(math.erf, otypes=[np.float64])
+
+    def cdf(x):
+        return np.mean(0.5 * (1.0 + erf((x[None, :] - mu) / (sd * math.sqrt(2.0)))), axis=0)
+
+    out = []
+    for p in (0.025, 0.975):
+        lo, hi = np.min(mu - 10.0 * sd, axis=0), np.max(mu + 10.0 * sd, axis=0)
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            below = cdf(mid) < p
+            lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
+        out.append(0.5 * (lo + hi))
+    return out[0], out[1]

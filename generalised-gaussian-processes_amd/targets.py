@@ -4,6 +4,9 @@
 share one density recipe -- PyMC3's log transform, its test point, the theta priors and the chain rule to the unconstrained
 variables -- which lives here once, beside the two pieces every target over a ``CollapsedBound`` shares (``composite.
 CompositeHmcTarget`` included): the single-launch evaluation and the test for the device-resident sampler.
+
+``SgpmcTarget`` (GPflow's SGPMC: theta and the whitened inducing values, what ``hmc.sample_hmc`` evaluates) has GPflow's softplus
+transforms and priors instead, and its own evaluation sequence over the whitened statistics.
 """
 from __future__ import annotations
 
@@ -12,7 +15,7 @@ import math
 import numpy as np
 import torch
 
-from .core import CollapsedBound, device_run_fits
+from .core import WHITENED_ROWS_MIN_WORK, CollapsedBound, SgpTimeoutError, device_run_fits, whitened_rows_layout
 
 _LOG_2_OVER_PI = math.log(2.0) - math.log(math.pi)
 _HALF_LOG_2PI = 0.9189385332046727
@@ -299,3 +302,168 @@ class JointHmcTarget(_LogThetaTarget):
             logp, grad = theta_logp_and_grad(th, ls, sf, sn, F, g["ls"].tolist(), g["sf2"], g["s2"])
             gz = g["Z"]
         return logp + zprior, grad + (gz.detach().to("cpu").numpy().reshape(-1) - zz).tolist()
+
+
+# ---------------------------------------------------------------------------------------------
+# SGPMC target: theta AND the whitened inducing values  (reference models/sgp_hmc.py:36-49; Hensman et al. 2015)
+# ---------------------------------------------------------------------------------------------
+_SGPMC_NOISE_FLOOR = 1e-6
+
+
+def _softplus(x):
+    return x + math.log1p(math.exp(-x)) if x > 0.0 else math.log1p(math.exp(x))
+
+
+def _sigmoid(x):
+    if x >= 0.0:
+        return 1.0 / (1.0 + math.exp(-x))
+    t = math.exp(x)
+    return t / (1.0 + t)
+
+
+def _softplus_inv(c):
+    return c + math.log(-math.expm1(-c))
+
+
+class SgpmcTarget:
+    """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values together (GPflow's ``SGPMC`` with a
+    Gaussian likelihood, models/sgp_hmc.py:38-43), q = [x_var | x_ls (d) | x_noise | v (M)] unconstrained, ndim = d + 2 + M.
+
+    kernel variance = softplus(x_var), lengthscales = softplus(x_ls), noise variance = 1e-6 + softplus(x_noise); Gamma(2, 1) on each
+    of the three evaluated at the constrained value plus log sigmoid(x) for the transform (models/sgp_hmc.py:47-49); v ~ N(0, I); K_uu
+    jitter 1e-5 (models/sgp_hmc.py:20).  [UPSTREAM] the transforms (softplus, the 1e-6 floor of the likelihood variance) and the prior
+    convention are GPflow's published behaviour as recalled: GPflow is not installed here and nothing was checked against it.
+
+    The density F(v, theta) is stated in include/sgp.h (sgp_sgpmc_from_whitened_stats).  One evaluation is ``kuu`` -> ``kuu_factor`` ->
+    ``suffstats_whitened`` (``suffstats_whitened_rows`` where ``core.whitened_rows_layout`` says so, T kept for pass 2) -> ``sgpmc_tail``
+    -> ``suffstats_bwd_factored`` -> ``kuu_bwd``, one result buffer and one device-to-host copy; transforms, priors and the chain rule to
+    x run on the host.  A non-zero ``kuu_factor`` status or a non-finite value gives (-inf, zeros), never an exception (a device
+    time-out still raises ``SgpTimeoutError``).  Stationary kernels, one process.  Z is fixed per evaluation and may be replaced
+    between evaluations (``set_Z``: the warm-up of ``sgp_hmc.train_sgp_hmc`` optimises it)."""
+
+    def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None):
+        from .core import _world
+        if kernel not in ("rbf", "matern32", "matern52"):
+            raise ValueError("SgpmcTarget takes the stationary kernels 'rbf', 'matern32', 'matern52' (got %r): composite kernels are "
+                             "not supported" % (kernel,))
+        if _world(group) > 1:
+            raise ValueError("SgpmcTarget runs in one process: a group of %d ranks is not supported" % _world(group))
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine(X.device if X.is_cuda else None)
+        self.engine = engine
+        if X.dim() == 1:
+            X = X[:, None]
+        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
+        self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
+        if self.X.shape[0] != self.y.shape[0]:
+            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
+        self.kernel = kernel
+        self.jitter = float(jitter)
+        self.d = int(self.X.shape[1])
+        self.N = int(self.X.shape[0])
+        self.whitened_rows_min_work = WHITENED_ROWS_MIN_WORK
+        self.last_pass1 = None   # "suffstats_whitened" / "suffstats_whitened_rows": which pass 1 the last evaluation ran
+        self.n_evals = 0
+        self._t_keep = None
+        self.set_Z(Z)
+
+    def set_Z(self, Z):
+        if Z.dim() == 1:
+            Z = Z[:, None]
+        Z = Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
+        if Z.shape[1] != self.d:
+            raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
+        self.Z = Z
+        self.M = int(Z.shape[0])
+        self.ndim = self.d + 2 + self.M
+
+    def start(self):
+        """GPflow's defaults as the reference sets them (models/sgp_hmc.py:36): variance log(2)^2, lengthscales log 2, likelihood
+        variance 1, v = 0."""
+        ln2 = math.log(2.0)
+        return [_softplus_inv(ln2 * ln2)] + [_softplus_inv(ln2)] * self.d + [_softplus_inv(1.0 - _SGPMC_NOISE_FLOOR)] + [0.0] * self.M
+
+    def constrain(self, q):
+        x = as_floats(q)
+        d = self.d
+        return {"variance": _softplus(x[0]), "lengthscales": [_softplus(t) for t in x[1:1 + d]],
+                "noise_variance": _SGPMC_NOISE_FLOOR + _softplus(x[1 + d]), "V": np.asarray(x[2 + d:], dtype=np.float64)}
+
+    def _t_for(self):
+        e = self.engine
+        if not hasattr(e, "kfu_buffer"):
+            return None
+        need = ((max(self.N, 1) + 255) // 256 * 256) * ((self.M + 127) // 128 * 128)
+        if self._t_keep is None or self._t_keep.numel() < need:
+            self._t_keep = e.kfu_buffer(self.N, self.M)
+        return self._t_keep
+
+    def _eval(self, q, want_grad, want_gz=False):
+        x = as_floats(q)
+        d, M, e = self.d, self.M, self.engine
+        if len(x) != self.ndim:
+            raise ValueError("the position has %d entries, expected d + 2 + M = %d" % (len(x), self.ndim))
+        bad = (-math.inf, [0.0] * self.ndim if want_grad else None, None)
+        if not all(math.isfinite(t) for t in x) or not all(abs(t) < 700.0 for t in x[:d + 2]):
+            return bad
+        sf2, ls, s2 = _softplus(x[0]), [_softplus(t) for t in x[1:1 + d]], _SGPMC_NOISE_FLOOR + _softplus(x[1 + d])
+        if not (sf2 > 0.0 and all(t > 0.0 for t in ls)):   # softplus underflowed: outside the representable range
+            return bad
+        self.n_evals += 1
+        ng = d + 1 + (M * d if want_gz else 0)
+        extra = ng + M if want_grad else 0
+        result = e.result_buffer(extra)
+        buf = result[0]
+        head = buf.numel() - extra
+        Z = self.Z
+        Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
+        linv, _ = e.kuu_factor(Kuu, info=result[2])   # the evaluation's status word is the K_uu status: the tail factors nothing
+        t_keep = None
+        if whitened_rows_layout(e, self.kernel, self.N, M, self.whitened_rows_min_work):
+            t_keep = self._t_for() if want_grad else None
+            packed = e.suffstats_whitened_rows(self.X, self.y, Z, ls, sf2, linv, self.kernel, t_out=t_keep)
+            self.last_pass1 = "suffstats_whitened_rows"
+        else:
+            packed = e.suffstats_whitened(self.X, self.y, Z, ls, sf2, linv, self.kernel)
+            self.last_pass1 = "suffstats_whitened"
+        v = torch.tensor(x[2 + d:], dtype=torch.float64).to(e.device)
+        res = e.sgpmc_tail(packed, v, s2, self.N, linv, with_adjoints=want_grad, result=result,
+                           **({"vbar_out": buf[head + ng:]} if want_grad else {}))
+        if want_grad:
+            g = buf[head:head + ng]
+            e.suffstats_bwd_factored(self.X, self.y, Z, ls, sf2, linv, res["Cw"], s2, res["bbar"], -1.0 / (2.0 * s2), self.kernel,
+                                     want_gz=want_gz, out=g, **({"t_in": t_keep} if t_keep is not None else {}))
+            e.kuu_bwd(Z, ls, sf2, res["Kuubar"], g, self.kernel, want_gz=want_gz)
+        host = buf.detach().to("cpu")   # the one host round trip
+        o, info = e.read_result(host)
+        if info < 0:
+            raise SgpTimeoutError()
+        F = float(o[0])
+        if info != 0 or not math.isfinite(F):
+            return bad
+        # priors at the constrained values + log sigmoid(x) for the transform
+        cons = [sf2] + ls + [s2]
+        sig = [_sigmoid(t) for t in x[:d + 2]]
+        if not all(s > 0.0 for s in sig):
+            return bad
+        logp = F + sum(math.log(c) - c for c in cons) + sum(math.log(s) for s in sig)
+        if not want_grad:
+            return logp, None, None
+        hl = host.tolist()
+        gh = hl[head:head + d + 1]
+        dF = [gh[d]] + gh[:d] + [float(o[3])]   # dF/d variance, dF/d lengthscales, dF/d s2 (SGP_SGPMC_OUT_S2BAR)
+        grad = [(dF[k] + 1.0 / cons[k] - 1.0) * sig[k] + (1.0 - sig[k]) for k in range(d + 2)] + hl[head + ng:head + ng + M]
+        if not all(math.isfinite(t) for t in grad):
+            return bad
+        gz = buf[head + d + 1:head + ng].reshape(M, d) if want_gz else None
+        return logp, grad, gz
+
+    def logp(self, q):
+        return self._eval(q, False)[0]
+
+    def logp_and_grad(self, q, want_gz=False):
+        """(logp, grad list[ndim]); with ``want_gz`` (the warm-up over Z as well) also dlogp/dZ, an M x d tensor on the engine's
+        device (None where the density is zero)."""
+        r = self._eval(q, True, want_gz)
+        return r if want_gz else r[:2]

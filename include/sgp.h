@@ -473,6 +473,36 @@ int sgp_bound_from_whitened_stats_ex(const double* W, const double* u, const dou
                                      const double* kuu_linv, int* info, double* Cw,
                                      void* ws, size_t ws_bytes, sgp_stream_t stream);
 
+/* ---- SGPMC: the joint density of the whitened inducing values and the data (Hensman et al. 2015) ----------------------------
+ * GPflow's SGPMC with a Gaussian likelihood (models/sgp_hmc.py:38-43): the sampler moves the hyper-parameters theta AND the whitened
+ * inducing values v (f_u = L v, v ~ N(0, I)).  In the notation of sgp_bound_from_whitened_stats -- K = K_uu + jitter I, L = chol(K),
+ * W = L^-1 Phi L^-T, u = L^-1 b, kappa = sum_n k(x_n, x_n) -- the value is
+ *   F(v, theta) = -N/2 log(2 pi s2) - (yy - 2 v.u + v^T W v + kappa - tr W) / (2 s2)      sum_n E_{p(f_n | v)} log N(y_n | f_n, s2)
+ *                 - 1/2 v.v - M/2 log(2 pi)                                                v ~ N(0, I)
+ * a function of the whitened statistics [W | u | yy | kappa] that sgp_suffstats_fwd_whitened(_rows) streams.  With
+ * h = (u - W v) / s2 its adjoints are
+ *   vbar = h - v          Cw = I - v v^T   (2 s2 Phibar = L^-T Cw L^-1: what sgp_suffstats_bwd_factored(_ex) takes)
+ *   bbar = L^-T v / s2    kappabar = -1 / (2 s2)    s2bar = -N / (2 s2) + (yy - 2 v.u + v^T W v + kappa - tr W) / (2 s2^2)
+ *   Kuubar = L^-T S' L^-1,  S' = -W / (2 s2) - sym(low(v h^T)),  low(A) = lower triangle with the diagonal halved, sym(A) = (A + A^T) / 2
+ * (bbar, Kuubar with respect to the UNwhitened b and K_uu, so sgp_suffstats_bwd_factored / sgp_kuu_bwd follow unchanged).  The low()
+ * term is the Cholesky adjoint: with whitened v the density depends on WHICH square root of K is used; it is a rank-one triangle
+ * because L^T (L^-T v) = v.  At fixed theta F is Gaussian in v with precision B = I + W / s2 and mode m = B^-1 u / s2, and
+ * F(m, theta) + M/2 log(2 pi) - 1/2 log det B is the collapsed bound of sgp_bound_from_whitened_stats at the same theta and jitter.
+ * Every array is a DEVICE array (v, vbar, bbar: M doubles; W, Cw, Kuubar: M x M, ld M); kuu_linv is the padded L^-1 of
+ * sgp_kuu_factor(_ex), whose status word covers this call as well: the tail factors nothing and owns no status.  Four launches (two
+ * with with_adjoints = 0, which needs none of vbar, Cw, bbar, Kuubar, kuu_linv); the same inputs give the same bits.             */
+#define SGP_SGPMC_OUT_F 0         /* F */
+#define SGP_SGPMC_OUT_DATA 1      /* the first line of F */
+#define SGP_SGPMC_OUT_PRIOR 2     /* the second line of F */
+#define SGP_SGPMC_OUT_S2BAR 3     /* dF/d s2 */
+#define SGP_SGPMC_OUT_KAPPABAR 4  /* dF/d kappa */
+#define SGP_SGPMC_OUT_LEN 5
+size_t sgp_sgpmc_workspace_bytes(int M);
+int sgp_sgpmc_from_whitened_stats(const double* W, const double* u, const double* yy, const double* kappa, const double* v,
+                                  double s2, int64_t N, int M, int with_adjoints, double* out, double* vbar, double* Cw,
+                                  double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
+                                  sgp_stream_t stream);
+
 /* ---- single-launch evaluation for small problems (M <= 128; stationary kernels d <= 24, composite d <= 8) -------------------------
  * The size class of the reference's own HMC runs (models/bayesian_sgpr_hmc.py:58-80,144-157: N ~ 250-1300, M = 100).
  * ONE cooperative kernel launch evaluates the bound and its gradient in the PyMC3 op order (A = L^-1 K_uf by blocked
