@@ -102,12 +102,17 @@ __global__ __launch_bounds__(256) void svgp_cols_kernel(const double* __restrict
   }
 }
 
-__device__ __forceinline__ double log_ndtr_dev(double z) { return log(0.5 * erfc(-z * 0.7071067811865476)); }
-// phi(z) / Phi(z), stable for the range Gauss-Hermite nodes reach
+// log Phi(z).  erfc underflows to 0 for z <= -38.6 (one mislabelled point against a confident mean reaches that at the outer
+// Gauss-Hermite node, 7.62, and the whole minibatch bound became -inf): for z < 0 the scaled complementary error function,
+// erfc(t) = erfcx(t) exp(-t^2), keeps the logarithm finite down to where z^2 / 2 itself overflows.
+__device__ __forceinline__ double log_ndtr_dev(double z) {
+  if (z < 0.0) return log(0.5 * erfcx(-z * 0.7071067811865476)) - 0.5 * z * z;
+  return log(0.5 * erfc(-z * 0.7071067811865476));
+}
+// phi(z) / Phi(z); for z < 0 it is sqrt(2 / pi) / erfcx(-z / sqrt 2), free of the 0 / 0 of the two underflowing factors
 __device__ __forceinline__ double mills_dev(double z) {
-  const double phi = 0.3989422804014327 * exp(-0.5 * z * z);
-  const double Phi = 0.5 * erfc(-z * 0.7071067811865476);
-  return Phi > 0.0 ? phi / Phi : -z;  // asymptote phi/Phi -> -z as z -> -inf
+  if (z < 0.0) return 0.7978845608028654 / erfcx(-z * 0.7071067811865476);
+  return 0.3989422804014327 * exp(-0.5 * z * z) / (0.5 * erfc(-z * 0.7071067811865476));
 }
 
 // per-point expected log-likelihood and its derivatives; fixed grid of 64 blocks, partial sums per block

@@ -32,10 +32,10 @@ LOG2PI = np.log(2 * np.arccos(LD(-1)))  # log(2 pi) in long double
 NOISE_FLOOR = 1e-6
 
 
-def chol_ld(K):
-    """Lower Cholesky factor in long double (numpy.linalg has no longdouble kernels): row by row."""
+def chol_ld(K, dtype=LD):
+    """Lower Cholesky factor in long double (numpy.linalg has no longdouble kernels): row by row.  (``dtype``: the same loop in float64.)"""
     M = K.shape[0]
-    L = np.zeros((M, M), LD)
+    L = np.zeros((M, M), dtype)
     for i in range(M):
         for j in range(i):
             L[i, j] = (K[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
@@ -46,10 +46,10 @@ def chol_ld(K):
     return L
 
 
-def tri_inv_ld(L):
+def tri_inv_ld(L, dtype=LD):
     """L^-1 by forward substitution in long double."""
     M = L.shape[0]
-    Li = np.zeros((M, M), LD)
+    Li = np.zeros((M, M), dtype)
     for i in range(M):
         Li[i, i] = 1 / L[i, i]
         if i:
