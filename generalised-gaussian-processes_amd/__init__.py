@@ -9,12 +9,12 @@ from .composite import (CO2_LOG_PRIOR_SD, CompositeBayesianSparseGPR_HMC, Compos
 from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
 from . import datasets, experiment_tools  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
-                      MultivariateNormal, RBFKernel, ScaleKernel, ZeroMean, settings)
+                      MultivariateNormal, PoissonLikelihood, RBFKernel, ScaleKernel, ZeroMean, settings)
 from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_device  # noqa: F401
 from .metrics import negative_log_predictive_mixture_density, nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
-from .sgp_hmc import SgpmcModel, get_posterior_predictive_uncertainty_intervals, predict_sgpmc, train_sgp_hmc  # noqa: F401
+from .sgp_hmc import SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments, predict_sgpmc, train_sgp_hmc  # noqa: F401
 from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget  # noqa: F401
 
 

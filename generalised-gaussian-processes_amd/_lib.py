@@ -15,6 +15,8 @@ SGP_ABI_VERSION = 3
 SGP_MAX_DIM = 32
 SGP_MAX_INDUCING = 4096
 KERNEL_IDS = {"rbf": 0, "matern32": 1, "matern52": 2, "composite": 3}
+LIKELIHOOD_IDS = {"gaussian": 0, "bernoulli": 1, "bernoulli_logit": 2, "poisson": 3}  # SGP_LIK_* ("bernoulli" = the probit link)
+SGPMC_LIK_OUT_LEN = 3
 COMP_LEN = 33  # SGP_COMP_LEN: doubles in a composite-kernel parameter block (include/sgp.h)
 OPT_CONTRACTION, OPT_ASM_OVERLAP, OPT_KFU_BUDGET_BYTES, OPT_COND_LIMIT, OPT_CU_BUDGET, OPT_TIMING, OPT_SHARED_DEVICE = range(7)
 OUT_F, OUT_LOGMARG, OUT_TRACE, OUT_LOGDETB, OUT_QUAD, OUT_TRW, OUT_S2BAR, OUT_KAPPABAR, OUT_LEN = range(9)
@@ -142,6 +144,12 @@ PROTOTYPES = {
     # SGPMC: the joint density of the whitened inducing values and the data, from the whitened statistics
     "sgp_sgpmc_workspace_bytes": (_sz, [_i32]),
     "sgp_sgpmc_from_whitened_stats": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # ... with a non-conjugate likelihood: the row pass over T = K'_fu L^-T and its M x M tail
+    "sgp_sgpmc_lik_rows_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_sgpmc_lik_rows": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _dbl, _dbl, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_sgpmc_lik_workspace_bytes": (_sz, [_i32]),
+    "sgp_sgpmc_lik_tail": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_suffstats_bwd_factored_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "sgp_suffstats_bwd_factored": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _dbl, _vp, _vp, _dbl, _vp, _dbl, _i64, _i32, _i32, _i32,
                                           _vp, _vp, _vp, _vp, _sz, _vp]),

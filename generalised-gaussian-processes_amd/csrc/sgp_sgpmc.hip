@@ -18,6 +18,9 @@ namespace sgp {
 //    smaller index is i and no wave waits for another's h.
 //  the next Mp / 64 blocks (adjoints only): t = L^-T v, a block per 64 columns, sixteen waves over the rows, the partial sums added in
 //    wave order.  The identity-padded rows of L^-1 meet v's zero padding: t is 0 there.
+// LIK (the tail of a non-conjugate likelihood, sgp_sgpmc_lik_tail): W := G and u := g arrive as the adjoints themselves, so h = g, the
+// triangle is S' = sym(G) - sym(low(v g^T)), only rows4's v_i^2 is used and no Cw is written; the t blocks are the same.
+template <bool LIK>
 __global__ __launch_bounds__(1024) void sgpmc_mid_kernel(const double* __restrict__ W, const double* __restrict__ u,
                                                          const double* __restrict__ v, const double* __restrict__ Li, int M, int Mp,
                                                          double s2, int with_adj, double* __restrict__ hvec,
@@ -30,22 +33,28 @@ __global__ __launch_bounds__(1024) void sgpmc_mid_kernel(const double* __restric
     const int i = b * 16 + wv;
     const bool live = i < M;
     double s = 0.0;
-    if (live)
-      for (int j = lane; j < M; j += 64) s = fma(W[(int64_t)i * M + j], v[j], s);
-    s = wave_sum(s);
+    if constexpr (!LIK) {
+      if (live)
+        for (int j = lane; j < M; j += 64) s = fma(W[(int64_t)i * M + j], v[j], s);
+      s = wave_sum(s);
+    }
     const double vi = live ? v[i] : 0.0;
-    const double hi = live ? (u[i] - s) / s2 : 0.0;
+    double hi;
+    if constexpr (LIK) hi = (live && with_adj) ? u[i] : 0.0;  // (a value-only call has neither G nor g)
+    else hi = live ? (u[i] - s) / s2 : 0.0;
     if (lane == 0) {
       hvec[i] = hi;
       rows4[i] = vi * s;
-      rows4[Mp + i] = live ? vi * u[i] : 0.0;
-      rows4[2 * Mp + i] = live ? W[(int64_t)i * M + i] : 0.0;
+      rows4[Mp + i] = (live && !LIK) ? vi * u[i] : 0.0;
+      rows4[2 * Mp + i] = (live && !LIK) ? W[(int64_t)i * M + i] : 0.0;
       rows4[3 * Mp + i] = vi * vi;
     }
     if (!with_adj) return;
-    if (live)
-      for (int c = lane; c < M; c += 64) Cw[(int64_t)i * M + c] = (c == i ? 1.0 : 0.0) - vi * v[c];
-    const double q = -0.5 / s2;
+    if constexpr (!LIK) {
+      if (live)
+        for (int c = lane; c < M; c += 64) Cw[(int64_t)i * M + c] = (c == i ? 1.0 : 0.0) - vi * v[c];
+    }
+    const double q = LIK ? 1.0 : -0.5 / s2;
     for (int c = i + lane; c < Mp; c += 64) {
       double val = 0.0;
       if (live && c < M) {
@@ -81,6 +90,8 @@ __global__ __launch_bounds__(1024) void sgpmc_mid_kernel(const double* __restric
 
 // The closing launch: blocks [0, nA) (adjoints only) write Kuubar = sym(R) cropped to M x M (ld M), R = L^-T S' L^-1 in the padded layout;
 // block 0 of them also bbar = t / s2 and vbar = h - v.  The last block adds the four row arrays up, each in one fixed order, and writes out.
+// LIK: yy points at the row pass's [sum ell | d sum ell / d s2 | sum dv] and the data term is its first entry; s2 = 1, so bbar = t.
+template <bool LIK>
 __global__ __launch_bounds__(256) void sgpmc_out_kernel(const double* __restrict__ R, const double* __restrict__ t,
                                                         const double* __restrict__ hvec, const double* __restrict__ v,
                                                         const double* __restrict__ rows4, const double* __restrict__ yy,
@@ -102,6 +113,15 @@ __global__ __launch_bounds__(256) void sgpmc_out_kernel(const double* __restrict
     const double vv = block_sum256(a3, red);
     if (threadIdx.x != 0) return;
     const double LOG2PI = 1.8378770664093453;
+    if constexpr (LIK) {
+      const double prior = -0.5 * vv - 0.5 * (double)M * LOG2PI;
+      out[SGP_SGPMC_OUT_F] = yy[0] + prior;
+      out[SGP_SGPMC_OUT_DATA] = yy[0];
+      out[SGP_SGPMC_OUT_PRIOR] = prior;
+      out[SGP_SGPMC_OUT_S2BAR] = yy[1];
+      out[SGP_SGPMC_OUT_KAPPABAR] = Nd > 0.0 ? yy[2] / Nd : 0.0;
+      return;
+    }
     const double Q = *yy - 2.0 * vu + vWv + *kappa - trW;
     const double data = -0.5 * Nd * (LOG2PI + log(s2)) - Q / (2.0 * s2);
     const double prior = -0.5 * vv - 0.5 * (double)M * LOG2PI;
@@ -165,7 +185,7 @@ extern "C" int sgp_sgpmc_from_whitened_stats(const double* W, const double* u, c
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int adj = with_adjoints ? 1 : 0;
-  sgpmc_mid_kernel<<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(W, u, v, kuu_linv, M, Mp, s2, adj, w.hvec, w.rows4, Cw, w.Sp, w.t);
+  sgpmc_mid_kernel<false><<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(W, u, v, kuu_linv, M, Mp, s2, adj, w.hvec, w.rows4, Cw, w.Sp, w.t);
   int nA = 0;
   if (adj) {
     const int64_t ld = Mp;
@@ -180,6 +200,39 @@ extern "C" int sgp_sgpmc_from_whitened_stats(const double* W, const double* u, c
     const int64_t g = ((int64_t)M * M + 255) / 256;
     nA = (int)(g < 2048 ? g : 2048);
   }
-  sgpmc_out_kernel<<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, yy, kappa, M, Mp, s2, (double)N, nA, Kuubar, bbar, vbar, out);
+  sgpmc_out_kernel<false><<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, yy, kappa, M, Mp, s2, (double)N, nA, Kuubar, bbar, vbar, out);
+  return check_launch();
+}
+
+// The tail behind sgp_sgpmc_lik_rows: the same four launches on (G, g) in place of (W, u).
+extern "C" size_t sgp_sgpmc_lik_workspace_bytes(int M) { return sgp_sgpmc_workspace_bytes(M); }
+
+extern "C" int sgp_sgpmc_lik_tail(const double* rows_out, const double* G, const double* g, const double* v, int64_t N, int M,
+                                  int with_adjoints, double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv,
+                                  void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!rows_out || !v || !out || M <= 0 || N < 0) return SGP_ERR_ARG;
+  if (with_adjoints && (!G || !g || !vbar || !bbar || !Kuubar || !kuu_linv)) return SGP_ERR_ARG;
+  if (M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  const int Mp = padded_m(M);
+  SgpmcWs w = carve_sgpmc(ws, Mp);
+  if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int adj = with_adjoints ? 1 : 0;
+  sgpmc_mid_kernel<true><<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(G, g, v, kuu_linv, M, Mp, 1.0, adj, w.hvec, w.rows4, nullptr, w.Sp, w.t);
+  int nA = 0;
+  if (adj) {
+    const int64_t ld = Mp;
+    GemmDesc t1;  // T = S' L^-1
+    t1.A = w.Sp; t1.lda = ld; t1.B = kuu_linv; t1.ldb = ld; t1.C = w.T; t1.ldc = ld;
+    t1.m = Mp; t1.n = Mp; t1.k = Mp; t1.klo_mask = 2;
+    gemm(t1, st);
+    GemmDesc t2;  // R = L^-T T
+    t2.A = kuu_linv; t2.lda = ld; t2.ta = true; t2.B = w.T; t2.ldb = ld; t2.C = w.R; t2.ldc = ld;
+    t2.m = Mp; t2.n = Mp; t2.k = Mp; t2.klo_mask = 1;
+    gemm(t2, st);
+    const int64_t gr = ((int64_t)M * M + 255) / 256;
+    nA = (int)(gr < 2048 ? gr : 2048);
+  }
+  sgpmc_out_kernel<true><<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, rows_out, nullptr, M, Mp, 1.0, (double)N, nA, Kuubar, bbar, vbar, out);
   return check_launch();
 }

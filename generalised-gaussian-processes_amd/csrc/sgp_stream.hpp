@@ -234,6 +234,33 @@ void stream_prologue(const StreamPlan& p, const KernArgs& ka, const double* X, i
 void stream_assemble(const StreamPlan& p, int kid, const double* Xs, const double* ys, const double* Zs, int64_t row0,
                      int64_t rows, int64_t N, int M, double* Kfu, double* bpart, hipStream_t st);
 
+// ---- the pieces of the whitened rows layout (sgp_suffstats_fwd_whitened_rows) that the SGPMC row pass (sgp_sgpmc_lik.hip) shares;
+// implemented in sgp_suffstats_fwd.hip
+struct Ctx;
+struct FwdWs {
+  double *Xs, *ys, *Zs, *Kfu, *slab, *bpart, *btmp, *yypart;
+  uint8_t* Q;  // digit planes of one super-chunk when the caller owns K'_fu (otherwise they live in Kfu)
+  size_t bytes;
+};
+// qrows: rows of one super-chunk of digit planes = the plan's sc_rows BEFORE a caller-owned K'_fu turns it into Npad
+FwdWs carve_fwd(void* ws, const StreamPlan& p, bool need_kfu, int64_t qrows);
+struct WhRowsWs {
+  FwdWs f;
+  double *R, *T;  // R = L^-T as a row-major operand; T = K'_fu R of one super-chunk (NULL when the caller owns it)
+  size_t bytes;
+};
+WhRowsWs carve_wh_rows(void* ws, const StreamPlan& p, bool caller_t);
+// the fp64 contraction of `nchunks` 16-row chunks of a row-major [rows x Mp] matrix into the per-split slabs (options of the context)
+void launch_syrk(const Ctx& cx, const double* K, int Mp, int64_t nchunks, const SplitMap& smap, int ntiles, int nsplit, int accum,
+                 double* slab, hipStream_t st);
+// out (M x M, ld M, both triangles) = scale * sum of the `nslabs` slabs, in a fixed order
+void reduce_slabs(const StreamPlan& p, const double* slab, int nslabs, int M, double scale, double* out, hipStream_t st);
+// bpart[row block][m] = sum over the block's ASM_ROWS rows of T[n][m] ys[n]  (tpart_kernel; T starts at row0, `rows` a multiple of ASM_ROWS)
+void launch_tpart(const double* T, const double* ys, int64_t row0, int64_t rows, int Mp, double* bpart, hipStream_t st);
+// b = sf2 * the fixed-order sum of `nparts` partials per ASM_ROWS row block, yy = the sum of yypart's 256 entries, kappa = sf2 N
+void reduce_bparts(const StreamPlan& p, const double* bpart, double* btmp, const double* yypart, int nparts, double sf2, int64_t N, int M,
+                   double* b, double* yy, double* kappa, hipStream_t st);
+
 // implemented in sgp_suffstats_i8.hip: the pass-1 contraction on the integer matrix cores (error-free digit planes of K'_fu)
 constexpr int I8_SPLIT_ROWS = 16384;  // rows per split at most: 7 digit pairs x 2^14 x 16384 rows < 2^31
 // splits of at most I8_SPLIT_ROWS rows (the int32 bound), a multiple of 8 (one XCD per residue), and -- when the rows allow

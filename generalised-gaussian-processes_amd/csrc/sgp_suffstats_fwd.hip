@@ -610,13 +610,8 @@ static bool i8_rule(int mode, int64_t Npad, int Mp) {
 }
 
 constexpr int BRED_G = 64;  // row groups of the two-stage b reduction
-struct FwdWs {
-  double *Xs, *ys, *Zs, *Kfu, *slab, *bpart, *btmp, *yypart;
-  uint8_t* Q;  // digit planes of one super-chunk when the caller owns K'_fu (otherwise they live in Kfu)
-  size_t bytes;
-};
 // qrows: rows of one super-chunk of digit planes = the plan's sc_rows BEFORE a caller-owned K'_fu turns it into Npad
-static FwdWs carve_fwd(void* ws, const StreamPlan& p, bool need_kfu, int64_t qrows) {
+FwdWs carve_fwd(void* ws, const StreamPlan& p, bool need_kfu, int64_t qrows) {
   Carver c(ws);
   FwdWs w;
   w.Xs = c.take<double>((size_t)(p.Npad > 0 ? p.Npad : 1) * p.DP);
@@ -637,7 +632,7 @@ static FwdWs carve_fwd(void* ws, const StreamPlan& p, bool need_kfu, int64_t qro
 }
 
 // the fp64 contraction of `nchunks` 16-row chunks of a row-major [rows x Mp] matrix into the per-split slabs (options of the context)
-static void launch_syrk(const Ctx& cx, const double* K, int Mp, int64_t nchunks, const SplitMap& smap, int ntiles, int nsplit, int accum,
+void launch_syrk(const Ctx& cx, const double* K, int Mp, int64_t nchunks, const SplitMap& smap, int ntiles, int nsplit, int accum,
                         double* slab, hipStream_t st) {
   const int skip_upper = cx.syrk_skip_upper;  // 0 = full diagonal tiles (A/B knob SGP_SYRK_SKIP_UPPER, read at context creation)
   const int nwaves = cx.syrk_waves, glds = cx.syrk_glds;
@@ -661,16 +656,23 @@ static void zero_slabs(const StreamPlan& p, const double* K, double* slab, hipSt
 // The fixed-order tail of pass 1 over a workspace with bpart / btmp / yypart.  finish_b: b = sf2 K'^T y from `nparts` partials per
 // ASM_ROWS row block (the fp64 assembly leaves asm_sub of them, the integer path's assembly and tpart_kernel one), yy and kappa;
 // finish_stats: Phi = sf2^2 K'^T K' from `nslabs` slabs first.
+void reduce_bparts(const StreamPlan& p, const double* bpart, double* btmp, const double* yypart, int nparts, double sf2, int64_t N, int M,
+                   double* b, double* yy, double* kappa, hipStream_t st) {
+  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(bpart, p.Npad / ASM_ROWS * nparts, p.Mp, BRED_G, btmp);
+  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(btmp, BRED_G, p.Mp, M, yypart, 256, sf2, sf2 * (double)N, b, yy, kappa);
+}
 template <typename Ws>
 static void finish_b(const StreamPlan& p, const Ws& w, int nparts, double sf2, int64_t N, int M, double* b, double* yy, double* kappa,
                      hipStream_t st) {
-  bpart_stage1_kernel<<<dim3(p.Mp / 64, BRED_G), 256, 0, st>>>(w.bpart, p.Npad / ASM_ROWS * nparts, p.Mp, BRED_G, w.btmp);
-  finalize_stats_kernel<<<(M + 255) / 256, 256, 0, st>>>(w.btmp, BRED_G, p.Mp, M, w.yypart, 256, sf2, sf2 * (double)N, b, yy, kappa);
+  reduce_bparts(p, w.bpart, w.btmp, w.yypart, nparts, sf2, N, M, b, yy, kappa, st);
+}
+void reduce_slabs(const StreamPlan& p, const double* slab, int nslabs, int M, double scale, double* Phi, hipStream_t st) {
+  const int nb32 = p.Mp / 32;
+  reduce_phi_kernel<<<nb32 * (nb32 + 1) / 2, 256, 0, st>>>(slab, nslabs, p.ntiles, M, scale, Phi);
 }
 static void finish_stats(const StreamPlan& p, const FwdWs& w, int nslabs, int nparts, double sf2, int64_t N, int M, double* Phi, double* b,
                          double* yy, double* kappa, hipStream_t st) {
-  const int nb32 = p.Mp / 32;
-  reduce_phi_kernel<<<nb32 * (nb32 + 1) / 2, 256, 0, st>>>(w.slab, nslabs, p.ntiles, M, sf2 * sf2, Phi);
+  reduce_slabs(p, w.slab, nslabs, M, sf2 * sf2, Phi, st);
   finish_b(p, w, nparts, sf2, N, M, b, yy, kappa, st);
 }
 
@@ -695,6 +697,9 @@ __global__ __launch_bounds__(256) void tpart_kernel(const double* __restrict__ T
     a3 = fma(__builtin_nontemporal_load(src + (size_t)(i + 3) * Mp), ysh[i + 3], a3);
   }
   bpart[((row0 + rbase) / ASM_ROWS) * Mp + m] = (a0 + a1) + (a2 + a3);
+}
+void launch_tpart(const double* T, const double* ys, int64_t row0, int64_t rows, int Mp, double* bpart, hipStream_t st) {
+  tpart_kernel<<<dim3((unsigned)(rows / ASM_ROWS), (Mp + 255) / 256), 256, 0, st>>>(T, ys, row0, Mp, bpart);
 }
 
 // ---- the extended streaming order (round 4): Phi to 2^-61, the triple product in double-double -------------------------------------
@@ -925,12 +930,7 @@ static ExtWs carve_ext(void* ws, const StreamPlan& p, int64_t qrows) {
   return w;
 }
 
-struct WhRowsWs {
-  FwdWs f;
-  double *R, *T;
-  size_t bytes;
-};
-static WhRowsWs carve_wh_rows(void* ws, const StreamPlan& p, bool caller_t) {
+WhRowsWs carve_wh_rows(void* ws, const StreamPlan& p, bool caller_t) {
   WhRowsWs w;
   w.f = carve_fwd(ws, p, true, 0);
   Carver c(ws ? static_cast<char*>(ws) + round_up64((int64_t)w.f.bytes, 256) : nullptr);
@@ -1125,7 +1125,7 @@ extern "C" int sgp_suffstats_fwd_whitened_rows(const double* X, int64_t ldx, con
     g.A = w.f.Kfu; g.lda = p.Mp; g.B = w.R; g.ldb = p.Mp; g.C = T; g.ldc = p.Mp;
     g.m = (int)rows; g.n = p.Mp; g.k = p.Mp; g.khi_mask = 2;
     gemm(g, st);
-    tpart_kernel<<<dim3((unsigned)(rows / ASM_ROWS), (p.Mp + 255) / 256), 256, 0, st>>>(T, w.f.ys, r0, p.Mp, w.f.bpart);
+    launch_tpart(T, w.f.ys, r0, rows, p.Mp, w.f.bpart, st);
     timing_begin(TIMING_SYRK, st);
     launch_syrk(cx, T, p.Mp, rows / NB, split_map(p.taper, rows / NB, p.nsplit), p.ntiles, p.nsplit, r0 > 0 ? 1 : 0, w.f.slab, st);
     timing_end(TIMING_SYRK, st);

@@ -8,57 +8,14 @@
 //   L = chol(Kuu + J I) ; A = L^-1 K_ub ; T = L_S^T A ; mu = A^T m ; v = k_bb - colsum(A o A) + colsum(T o T)
 //   ELBO / datum = mean_b E_{N(mu_b, v_b)} log p(y_b | f) - KL(N(m, L_S L_S^T) || N(0, I)) / N
 //
-// Likelihoods: Gaussian (closed form) and Bernoulli-probit (20-point Gauss-Hermite, y in {-1, +1}).
+// Likelihoods: the four of sgp_lik.hpp -- Gaussian and Poisson (closed form), Bernoulli probit / logit (20-point Gauss-Hermite, y in {-1, +1}).
 // The shapes are small (M <= a few hundred, B = minibatch), so this path is launch-latency bound; every
 // O(M^2 B) / O(M^3) product runs on the fp64-MFMA GEMM of sgp_dense.hip and the reverse pass is the
 // closed-form adjoint (Cholesky adjoint  Kbar = sym(L^-T Phi(L^T Lbar) L^-1), Murray 2016) -- no autograd.
 #include "sgp_dense.hpp"
+#include "sgp_lik.hpp"
 
 namespace sgp {
-
-constexpr int GH_N = 20;
-struct GHTable {
-  double x[GH_N];  // nodes of  int f(x) N(x; 0, 1) dx
-  double w[GH_N];  // weights (sum to 1)
-};
-// Gauss-Hermite nodes / weights by Newton iteration on the orthonormal Hermite recurrence (host, once):
-// physicists' rule (weight exp(-x^2)) rescaled to the standard normal:  x * sqrt(2),  w / sqrt(pi).
-static void gauss_hermite_host(int n, double* xs, double* ws) {
-  const double PIM4 = 0.7511255444649425;  // pi^(-1/4)
-  double z = 0.0, pp = 1.0;
-  const int half = (n + 1) / 2;
-  for (int i = 0; i < half; ++i) {
-    if (i == 0) z = sqrt(2.0 * n + 1.0) - 1.85575 * pow(2.0 * n + 1.0, -0.16667);
-    else if (i == 1) z -= 1.14 * pow((double)n, 0.426) / z;
-    else if (i == 2) z = 1.86 * z - 0.86 * xs[0];
-    else if (i == 3) z = 1.91 * z - 0.91 * xs[1];
-    else z = 2.0 * z - xs[i - 2];
-    for (int its = 0; its < 200; ++its) {
-      double p1 = PIM4, p2 = 0.0;
-      for (int j = 1; j <= n; ++j) {
-        const double p3 = p2;
-        p2 = p1;
-        p1 = z * sqrt(2.0 / j) * p2 - sqrt((double)(j - 1) / j) * p3;
-      }
-      pp = sqrt(2.0 * n) * p2;
-      const double z1 = z;
-      z = z1 - p1 / pp;
-      if (fabs(z - z1) <= 1e-15 * (1.0 + fabs(z))) break;
-    }
-    xs[i] = z;
-    xs[n - 1 - i] = -z;
-    ws[i] = ws[n - 1 - i] = 2.0 / (pp * pp);
-  }
-  for (int i = 0; i < n; ++i) {
-    xs[i] *= 1.4142135623730951;
-    ws[i] *= 0.5641895835477563;
-  }
-}
-static GHTable make_gh() {
-  GHTable t;
-  gauss_hermite_host(GH_N, t.x, t.w);
-  return t;
-}
 
 // Kub[m][b] = sf2 k'(z_m, x_b) (zero in the padding), Mp x Bp
 template <int KID>
@@ -102,19 +59,6 @@ __global__ __launch_bounds__(256) void svgp_cols_kernel(const double* __restrict
   }
 }
 
-// log Phi(z).  erfc underflows to 0 for z <= -38.6 (one mislabelled point against a confident mean reaches that at the outer
-// Gauss-Hermite node, 7.62, and the whole minibatch bound became -inf): for z < 0 the scaled complementary error function,
-// erfc(t) = erfcx(t) exp(-t^2), keeps the logarithm finite down to where z^2 / 2 itself overflows.
-__device__ __forceinline__ double log_ndtr_dev(double z) {
-  if (z < 0.0) return log(0.5 * erfcx(-z * 0.7071067811865476)) - 0.5 * z * z;
-  return log(0.5 * erfc(-z * 0.7071067811865476));
-}
-// phi(z) / Phi(z); for z < 0 it is sqrt(2 / pi) / erfcx(-z / sqrt 2), free of the 0 / 0 of the two underflowing factors
-__device__ __forceinline__ double mills_dev(double z) {
-  if (z < 0.0) return 0.7978845608028654 / erfcx(-z * 0.7071067811865476);
-  return 0.3989422804014327 * exp(-0.5 * z * z) / (0.5 * erfc(-z * 0.7071067811865476));
-}
-
 // per-point expected log-likelihood and its derivatives; fixed grid of 64 blocks, partial sums per block
 __global__ __launch_bounds__(256) void svgp_ell_kernel(const double* __restrict__ y, const double* __restrict__ mu,
                                                        const double* __restrict__ v, int B, double s2, int lik, GHTable gh,
@@ -124,25 +68,8 @@ __global__ __launch_bounds__(256) void svgp_ell_kernel(const double* __restrict_
   double se = 0.0, ss = 0.0;
   for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
     const double yb = y[b], m = mu[b], vv = v[b];
-    double ell, gm, gv, gs = 0.0;
-    if (lik == 0) {
-      const double r = yb - m, q = r * r + vv;
-      ell = -0.9189385332046727 - 0.5 * log(s2) - q / (2.0 * s2);
-      gm = r / s2;
-      gv = -0.5 / s2;
-      gs = -0.5 / s2 + q / (2.0 * s2 * s2);
-    } else {
-      const double sd = sqrt(vv);
-      ell = 0.0; gm = 0.0; gv = 0.0;
-      for (int i = 0; i < GH_N; ++i) {
-        const double z = yb * (m + sd * gh.x[i]);
-        ell = fma(gh.w[i], log_ndtr_dev(z), ell);
-        const double r = gh.w[i] * yb * mills_dev(z);
-        gm += r;
-        gv = fma(r, gh.x[i], gv);
-      }
-      gv = gv / (2.0 * sd);
-    }
+    double ell, gm, gv, gs;
+    lik_eval(lik, yb, m, vv, s2, gh, ell, gm, gv, gs);
     dmu[b] = gm;
     dv[b] = gv;
     se += ell;
@@ -509,25 +436,8 @@ __global__ __launch_bounds__(256) void svgp_ell_batch_kernel(const double* __res
   double se = 0.0, ss = 0.0;
   for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
     const double yb = y[b], m = mu[b], vv = v[b];
-    double ell, gm, gv, gs = 0.0;
-    if (lik == 0) {
-      const double r = yb - m, q = r * r + vv;
-      ell = -0.9189385332046727 - 0.5 * log(s2) - q / (2.0 * s2);
-      gm = r / s2;
-      gv = -0.5 / s2;
-      gs = -0.5 / s2 + q / (2.0 * s2 * s2);
-    } else {
-      const double sd = sqrt(vv);
-      ell = 0.0; gm = 0.0; gv = 0.0;
-      for (int i = 0; i < GH_N; ++i) {
-        const double z = yb * (m + sd * gh.x[i]);
-        ell = fma(gh.w[i], log_ndtr_dev(z), ell);
-        const double r = gh.w[i] * yb * mills_dev(z);
-        gm += r;
-        gv = fma(r, gh.x[i], gv);
-      }
-      gv = gv / (2.0 * sd);
-    }
+    double ell, gm, gv, gs;
+    lik_eval(lik, yb, m, vv, s2, gh, ell, gm, gv, gs);
     dmu[b] = gm;
     dv[b] = gv;
     se += ell;
@@ -932,7 +842,7 @@ extern "C" int sgp_svgp_elbo(const double* Xb, int64_t ldx, const double* yb, in
   if (!Xb || !yb || !Z || !inv_ls || !m || !LS || !out || !info || B <= 0 || M <= 0 || d <= 0 || ldx < d || ldz < d ||
       N_total <= 0)
     return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_MATERN52 || likelihood_id < 0 || likelihood_id > 1) return SGP_ERR_ARG;
+  if (kernel_id < 0 || kernel_id > SGP_KERNEL_MATERN52 || likelihood_id < 0 || likelihood_id > LIK_ID_MAX) return SGP_ERR_ARG;
   if (likelihood_id == 0 && !(s2 > 0.0)) return SGP_ERR_ARG;
   if (with_grads && (!g_m || !g_LS || !g_Z || !g_ls || !g_sf2 || !g_s2)) return SGP_ERR_ARG;
   if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING || B > (1 << 20)) return SGP_ERR_DIM;
@@ -1015,7 +925,7 @@ static int svgp_batch_impl(int phase, const double* Xb, int64_t ldx, const doubl
   if (fwd && (!out || !info)) return SGP_ERR_ARG;
   if (predict && !g_m) return SGP_ERR_ARG;
   if (S < 1 || S > SVGP_MAX_S) return SGP_ERR_ARG;
-  if (kernel_id < 0 || kernel_id > SGP_KERNEL_MATERN52 || likelihood_id < 0 || likelihood_id > 1) return SGP_ERR_ARG;
+  if (kernel_id < 0 || kernel_id > SGP_KERNEL_MATERN52 || likelihood_id < 0 || likelihood_id > LIK_ID_MAX) return SGP_ERR_ARG;
   if (with_grads && (!g_m || !g_LS || !g_Z || !g_ls || !g_sf2)) return SGP_ERR_ARG;
   if (d > SGP_MAX_DIM || M > SGP_MAX_INDUCING || B > (1 << 20)) return SGP_ERR_DIM;
   SvgpThetaS th{};

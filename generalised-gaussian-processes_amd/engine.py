@@ -33,6 +33,14 @@ def _kernel_id(kernel) -> int:
         raise ValueError("unknown kernel %r (expected one of %s)" % (kernel, sorted(KERNEL_IDS))) from None
 
 
+def _likelihood_id(likelihood) -> int:
+    """SGP_LIK_* of a likelihood name ("bernoulli" = "bernoulli_probit")."""
+    name = "bernoulli" if likelihood == "bernoulli_probit" else likelihood
+    if name not in _lib.LIKELIHOOD_IDS:
+        raise ValueError("unknown likelihood %r (known: %s)" % (likelihood, ", ".join(sorted(_lib.LIKELIHOOD_IDS))))
+    return _lib.LIKELIHOOD_IDS[name]
+
+
 class HipEngine:
     """Calls the HIP library on ``device`` (default: current CUDA device).  No CPU fallback.
 
@@ -475,6 +483,61 @@ class HipEngine:
         _lib.check("sgp_sgpmc_from_whitened_stats", st)
         return res
 
+    def sgpmc_lik_rows(self, X, y, Z, ls, sf2, s2, v, kuu_linv, t_out, kernel="rbf", likelihood="poisson", want_adjoints=False):
+        """The SGPMC row pass of a non-conjugate likelihood (include/sgp.h: sgp_sgpmc_lik_rows): the conditional moments of every
+        datum from T = K'_fu L^-T, the likelihood layer, and the M-sized adjoints.  ``t_out`` (from ``kfu_buffer``) is required: it
+        holds T on return, diag(dv) T with the adjoints -- what ``suffstats_bwd_factored(..., t_in=)`` takes.
+
+        Returns dict(out = [sum ell | d sum ell / d s2 | sum dv], dmu, dv (N doubles), and with the adjoints g (M), G (M x M)).
+        Nothing is synchronised."""
+        N, d = X.shape
+        M = Z.shape[0]
+        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv"), self._chk(v, "v"), self._chk(t_out, "t_out")
+        if N > 0:
+            self._chk(X, "X"), self._chk(y, "y")
+        if v.numel() != M:
+            raise ValueError("v has %d entries, Z has %d rows" % (v.numel(), M))
+        if t_out.numel() < self.lib.sgp_kfu_len(N, M):
+            raise ValueError("t_out holds %d doubles, sgp_kfu_len(N, M) = %d" % (t_out.numel(), self.lib.sgp_kfu_len(N, M)))
+        nbytes = self._cf.sgp_sgpmc_lik_rows_workspace_bytes(N, M, d)
+        if nbytes == 0:
+            raise ValueError("unsupported shape N=%d M=%d d=%d (the shard's K'_fu must fit one super-chunk)" % (N, M, d))
+        ws = self._workspace("sgpmc_lik_rows", nbytes)
+        res = {"out": self.empty(_lib.SGPMC_LIK_OUT_LEN), "dmu": self.empty(N), "dv": self.empty(N)}
+        if want_adjoints:
+            res.update(g=self.empty(M), G=self.empty(M, M))
+        st = self._cf.sgp_sgpmc_lik_rows(
+            self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), float(s2), self._ptr(v), N, M, d,
+            _kernel_id(kernel), _likelihood_id(likelihood), self._ptr(kuu_linv), 1 if want_adjoints else 0, self._ptr(res["out"]),
+            self._ptr(res.get("G")), self._ptr(res.get("g")), self._ptr(res["dmu"]), self._ptr(res["dv"]), self._ptr(t_out),
+            self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_lik_rows", st)
+        return res
+
+    def sgpmc_lik_tail(self, rows, v, N, kuu_linv, with_adjoints=False, result=None, vbar_out=None):
+        """The M x M tail behind ``sgpmc_lik_rows`` (include/sgp.h: sgp_sgpmc_lik_tail) on its result ``rows``.
+
+        Returns dict(out = [F | sum ell | prior-of-v term | d sum ell / d s2 | (sum dv) / N] in the head of ``buf``, info, buf, and with
+        the adjoints vbar, bbar, Kuubar).  ``result`` / ``vbar_out`` as for ``sgpmc_tail``.  Nothing is synchronised."""
+        M = int(v.numel())
+        self._chk(v, "v")
+        buf, out, info = result if result is not None else self.result_buffer()
+        res = {"out": out, "info": info, "buf": buf}
+        vbar = bbar = Kuubar = None
+        if with_adjoints:
+            if kuu_linv is None or "G" not in rows:
+                raise ValueError("sgpmc_lik_tail(with_adjoints=True) needs kuu_linv and the adjoints of sgpmc_lik_rows")
+            self._chk(kuu_linv, "kuu_linv")
+            vbar, bbar, Kuubar = vbar_out if vbar_out is not None else self.empty(M), self.empty(M), self.empty(M, M)
+            res.update(vbar=vbar, bbar=bbar, Kuubar=Kuubar)
+        ws = self._workspace("sgpmc", self.lib.sgp_sgpmc_lik_workspace_bytes(M))
+        st = self.lib.sgp_sgpmc_lik_tail(
+            self._ptr(rows["out"]), self._ptr(rows.get("G")), self._ptr(rows.get("g")), self._ptr(v), int(N), M,
+            1 if with_adjoints else 0, self._ptr(out), self._ptr(vbar), self._ptr(bbar), self._ptr(Kuubar), self._ptr(kuu_linv),
+            self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_lik_tail", st)
+        return res
+
     # ------------------------------------------------------------------ single-launch path for small problems
     def small_supported(self, N: int, M: int, d: int, kernel="rbf") -> bool:
         return bool(self._cf.sgp_small_supported(int(N), int(M), int(d), _kernel_id(kernel)))
@@ -794,7 +857,7 @@ class HipEngine:
         M = Z.shape[0]
         for t, n in ((Xb, "Xb"), (yb, "yb"), (Z, "Z"), (m, "m"), (LS, "LS")):
             self._chk(t, n)
-        lik = {"gaussian": 0, "bernoulli": 1, "bernoulli_probit": 1}[likelihood]
+        lik = _likelihood_id(likelihood)
         out = self.empty(3)
         info = torch.zeros(1, dtype=torch.int32, device=self.device)
         res = {"out": out, "info": info}
@@ -829,7 +892,7 @@ class HipEngine:
         S = len(lsv)
         if any(len(row) != d for row in lsv) or len(sf2) != S or len(s2) != S:
             raise ValueError("ls must be S x d, sf2 and s2 of length S")
-        lik = {"gaussian": 0, "bernoulli": 1, "bernoulli_probit": 1}[likelihood]
+        lik = _likelihood_id(likelihood)
         inv = (ctypes.c_double * (S * d))(*[1.0 / v for row in lsv for v in row])
         sf2c = (ctypes.c_double * S)(*[float(v) for v in sf2])
         s2c = (ctypes.c_double * S)(*[float(v) for v in s2])

@@ -142,17 +142,44 @@ class GaussianLikelihood(nn.Module):
 
 
 class BernoulliLikelihood(nn.Module):
-    """Probit link, labels in {-1, +1} inside the bound ({0, 1} inputs are mapped); no noise parameter
-    (the reference's classification scratch uses gpytorch.likelihoods.BernoulliLikelihood, scratch_pymc3.py:78-88)."""
+    """Probit (default) or logit link, labels in {-1, +1} inside the bound ({0, 1} inputs are mapped); no noise parameter
+    (the reference's classification scratch uses gpytorch.likelihoods.BernoulliLikelihood, scratch_pymc3.py:78-88; its data
+    generator draws binary labels through the logit link, utils/load_data.py:89-99)."""
     name = "bernoulli"
+
+    def __init__(self, link="probit"):
+        super().__init__()
+        if link not in ("probit", "logit"):
+            raise ValueError("link must be 'probit' or 'logit' (got %r)" % (link,))
+        self.link = link
+        self.name = "bernoulli" if link == "probit" else "bernoulli_logit"
 
     def forward(self, dist):
         return self(dist)
 
     def __call__(self, dist):
+        if self.link == "logit":  # predictive class-1 probability by the 20-point Gauss-Hermite rule the bound uses
+            import numpy as np
+            x, w = np.polynomial.hermite_e.hermegauss(20)
+            x = torch.as_tensor(x, dtype=dist.loc.dtype, device=dist.loc.device)
+            w = torch.as_tensor(w / (2.0 * np.pi) ** 0.5, dtype=dist.loc.dtype, device=dist.loc.device)
+            return torch.sigmoid(dist.loc[..., None] + torch.sqrt(dist.variance)[..., None] * x) @ w
         # predictive class-1 probability  Phi(mu / sqrt(1 + v))
         z = dist.loc / torch.sqrt(1.0 + dist.variance)
         return 0.5 * torch.erfc(-z * 0.7071067811865476)
+
+
+class PoissonLikelihood(nn.Module):
+    """Counts with a log link, y ~ Poisson(exp f); no noise parameter (the reference's data generator draws such counts,
+    utils/load_data.py:61-62)."""
+    name = "poisson"
+
+    def forward(self, dist):
+        return self(dist)
+
+    def __call__(self, dist):
+        # predictive mean count  E exp(f) = exp(mu + v / 2)
+        return torch.exp(dist.loc + 0.5 * dist.variance)
 
 
 class InducingPointKernel(nn.Module):

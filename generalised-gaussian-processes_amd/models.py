@@ -620,11 +620,15 @@ class StochasticVariationalGP(torch.nn.Module):
             self._engine = HipEngine(self.train_x.device if self.train_x.is_cuda else None)
         return self._engine
 
+    def _noise_free(self):
+        """The likelihood has no noise parameter (Bernoulli, Poisson): the bound's s2 argument is the constant 1 it ignores."""
+        return not hasattr(self.likelihood, "noise")
+
     def _theta_row(self):
         """[outputscale | lengthscales | noise variance] as a 1 x (d + 2) host tensor (differentiable wrt the raw parameters)."""
         sf2 = self.covar_module.outputscale.reshape(1)
         ls = self.covar_module.base_kernel.lengthscale.reshape(-1)
-        if getattr(self.likelihood, "name", "gaussian") == "bernoulli":
+        if self._noise_free():
             s2 = torch.ones(1, dtype=torch.float64, device=sf2.device)
         else:
             s2 = self.likelihood.noise.reshape(1).to(sf2.device)
@@ -648,14 +652,14 @@ class StochasticVariationalGP(torch.nn.Module):
         if x_batch.dim() == 1:
             x_batch = x_batch[:, None]
         yb = self._dev(y_batch).reshape(-1)
-        if getattr(self.likelihood, "name", "gaussian") == "bernoulli":
+        if getattr(self.likelihood, "name", "gaussian") in ("bernoulli", "bernoulli_logit"):
             yb = torch.where(yb > 0, torch.ones_like(yb), -torch.ones_like(yb))
         if getattr(self, "batched", True) and hasattr(self._engine_obj(), "svgp_elbo_batch"):
             # the batched chain with one sample: a host tensor comes back (the bound and its status word in one copy; inside a
             # training loop asynchronously, see train_model)
             return _SVGPBatchBoundFn.apply(self._theta_row(), self.inducing_inputs, self.variational_mean, self.chol_variational_covar,
                                            self, self._dev(x_batch), yb)[0]
-        if getattr(self.likelihood, "name", "gaussian") == "bernoulli":
+        if self._noise_free():
             s2 = torch.ones(1, dtype=torch.float64, device=yb.device)
         else:
             s2 = self.likelihood.noise
@@ -708,7 +712,7 @@ class StochasticVariationalGP(torch.nn.Module):
         self.likelihood.eval()
         with torch.no_grad():
             mean, var = self.latent_predictive(test_x)
-            if getattr(self.likelihood, "name", "gaussian") == "bernoulli":
+            if self._noise_free():
                 return self.likelihood(MultivariateNormal(mean, None, variance=var))
             return MultivariateNormal(mean, None, variance=var + self.likelihood.noise.detach().to(var.device))
 
@@ -767,6 +771,9 @@ class BayesianStochasticVariationalGP(StochasticVariationalGP):
         self.n = self.num_data
         self.input_dim = self.train_x.shape[1]
         self.num_hyper_samples = num_hyper_samples
+        if getattr(self.likelihood, "name", "gaussian") not in ("gaussian", "bernoulli"):
+            raise ValueError("BayesianStochasticVariationalGP takes the Gaussian and the Bernoulli-probit likelihood (got %r)"
+                             % (getattr(self.likelihood, "name", None),))
         self.bernoulli = getattr(self.likelihood, "name", "gaussian") == "bernoulli"
         self.hyper_dim = self.input_dim + (1 if self.bernoulli else 2)
         self.log_theta = VariationalHyperDist(self.hyper_dim, prior_var=0.01, n=self.n, seed=seed)

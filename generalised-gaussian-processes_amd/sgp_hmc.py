@@ -1,6 +1,7 @@
 """SGPMC + HMC ("JointHMC"): the third sampler row of the reference's tables (models/sgp_hmc.py; Hensman et al. 2015).
 
-GPflow's ``SGPMC`` with a Gaussian likelihood, sampled jointly over the hyper-parameters and the whitened inducing values by
+GPflow's ``SGPMC`` with a Gaussian likelihood (the reference's), or with a Bernoulli (probit / logit) or Poisson likelihood -- the
+non-conjugate case SGPMC exists for -- sampled jointly over the hyper-parameters and the whitened inducing values by
 fixed-length HMC with TFP's simple step-size adaptation.  Here the density is ``targets.SgpmcTarget`` (the whitened sufficient
 statistics streamed by pass 1, the SGPMC tail of include/sgp.h, the factored pass 2) and the sampler ``hmc.sample_hmc``.
 
@@ -29,6 +30,7 @@ class SgpmcModel:
         self.engine = target.engine
         self.kernel = target.kernel
         self.jitter = target.jitter
+        self.likelihood = target.likelihood
         self.warmup = {}
 
     @property
@@ -41,8 +43,9 @@ def _as_tensor(a):
     return t.to(torch.float64)
 
 
-def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed=None, warmup_iters=100):
-    """models/sgp_hmc.py:32-91.  ``data`` = (X_train, Y_train); returns ``(model, trace, wall_clock_secs)``.
+def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed=None, warmup_iters=100, likelihood="gaussian"):
+    """models/sgp_hmc.py:32-91.  ``data`` = (X_train, Y_train); returns ``(model, trace, wall_clock_secs)``.  ``likelihood``:
+    "gaussian" (the reference's), "bernoulli" (probit), "bernoulli_logit" or "poisson" (``targets.SgpmcTarget``).
 
     As the reference: (1) a warm-up, ``scipy.optimize.minimize(method="L-BFGS-B", jac=True, maxiter=warmup_iters)`` on -logp over
     every variable INCLUDING the inducing inputs (:54-55; gpflow.optimizers.Scipy's default method); (2) Z is frozen (:56); (3)
@@ -57,7 +60,7 @@ def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed
         Z0 = Z0[:, None]
     if X.shape[1] != int(input_dims) or Z0.shape[1] != int(input_dims):
         raise ValueError("input_dims = %d, X has %d columns, Z_init has %d" % (int(input_dims), X.shape[1], Z0.shape[1]))
-    target = SgpmcTarget(X, Y, Z0, kernel="rbf", jitter=1e-5, engine=engine)   # SquaredExponential, jitter 1e-5 (:20, :36)
+    target = SgpmcTarget(X, Y, Z0, kernel="rbf", jitter=1e-5, engine=engine, likelihood=likelihood)   # SquaredExponential, jitter 1e-5 (:20, :36)
     model = SgpmcModel(target)
     M, d, nd = target.M, target.d, target.ndim
     dev = target.engine.device
@@ -84,11 +87,32 @@ def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed
     return model, trace, wall_clock_secs
 
 
+def likelihood_moments(likelihood, mu, var):
+    """(E y, sd y) of y | f ~ likelihood with f ~ N(mu, var), elementwise:
+    Bernoulli (y in {0, 1}): p and sqrt(p (1 - p)) with p = Phi(mu / sqrt(1 + var)) for the probit link, the 20-point Gauss-Hermite
+    mean of sigmoid(f) for the logit link; Poisson (log link): m = exp(mu + var / 2) and sqrt(m + (e^var - 1) m^2)."""
+    mu, var = np.asarray(mu, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    if likelihood == "poisson":
+        m = np.exp(mu + 0.5 * var)
+        return m, np.sqrt(m + np.expm1(var) * m * m)
+    if likelihood == "bernoulli":
+        erf = np.vectorize(math.erf, otypes=[np.float64])
+        p = 0.5 * (1.0 + erf(mu / np.sqrt(1.0 + var) / math.sqrt(2.0)))
+    elif likelihood == "bernoulli_logit":
+        x, w = np.polynomial.hermite_e.hermegauss(20)
+        f = mu[..., None] + np.sqrt(var)[..., None] * x
+        p = (0.5 * (1.0 + np.tanh(0.5 * f))) @ (w / math.sqrt(2.0 * math.pi))
+    else:
+        raise ValueError("no conditional moments for the likelihood %r" % (likelihood,))
+    return p, np.sqrt(p * (1.0 - p))
+
+
 def predict_sgpmc(model, trace, X_test, n_draws=50):
     """models/sgp_hmc.py:93-130: ``(pred_mean, f_means, y_stds)``, the last two (draws x test points).  The reference predicts from
     the FIRST 50 draws of the chain; ``n_draws`` keeps that default (fewer when the trace is shorter).  Per draw ``predict_f`` is the
     whitened SVGP predictive with q(v) a point mass, ``engine.svgp_predict(m=v, LS=0)``: mean = a^T v, var = k** - |a|^2 with
-    a = L^-1 k_u*; y_std = sqrt(var + noise variance)."""
+    a = L^-1 k_u*; y_std = sqrt(var + noise variance).  With a non-Gaussian likelihood ``f_means`` and ``y_stds`` hold the likelihood's
+    conditional moments of y per draw (``likelihood_moments``) and ``pred_mean`` their mean over the draws."""
     e = model.engine
     Xs = _as_tensor(X_test)
     if Xs.dim() == 1:
@@ -106,8 +130,14 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
         m = torch.as_tensor(np.asarray(row["V"], dtype=np.float64)).to(e.device).contiguous()
         mean, var, _ = e.svgp_predict(Xs, Z, [float(t) for t in np.asarray(row["lengthscales"]).reshape(-1)], float(row["variance"]), m, LS,
                                       jitter=model.jitter, kernel=model.kernel)
-        f_means.append(mean.detach().to("cpu").numpy())
-        y_stds.append(np.sqrt(np.maximum(var.detach().to("cpu").numpy(), 0.0) + float(row["noise_variance"])))
+        mean, var = mean.detach().to("cpu").numpy(), np.maximum(var.detach().to("cpu").numpy(), 0.0)
+        if model.likelihood == "gaussian":
+            f_means.append(mean)
+            y_stds.append(np.sqrt(var + float(row["noise_variance"])))
+        else:
+            ym, ys = likelihood_moments(model.likelihood, mean, var)
+            f_means.append(ym)
+            y_stds.append(ys)
     f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
     return np.mean(f_means, axis=0), f_means, y_stds
 

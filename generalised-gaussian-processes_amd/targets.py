@@ -326,8 +326,8 @@ def _softplus_inv(c):
 
 
 class SgpmcTarget:
-    """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values together (GPflow's ``SGPMC`` with a
-    Gaussian likelihood, models/sgp_hmc.py:38-43), q = [x_var | x_ls (d) | x_noise | v (M)] unconstrained, ndim = d + 2 + M.
+    """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values together (GPflow's ``SGPMC``, with a
+    Gaussian likelihood models/sgp_hmc.py:38-43), q = [x_var | x_ls (d) | x_noise | v (M)] unconstrained, ndim = d + 2 + M.
 
     kernel variance = softplus(x_var), lengthscales = softplus(x_ls), noise variance = 1e-6 + softplus(x_noise); Gamma(2, 1) on each
     of the three evaluated at the constrained value plus log sigmoid(x) for the transform (models/sgp_hmc.py:47-49); v ~ N(0, I); K_uu
@@ -339,10 +339,24 @@ class SgpmcTarget:
     -> ``suffstats_bwd_factored`` -> ``kuu_bwd``, one result buffer and one device-to-host copy; transforms, priors and the chain rule to
     x run on the host.  A non-zero ``kuu_factor`` status or a non-finite value gives (-inf, zeros), never an exception (a device
     time-out still raises ``SgpTimeoutError``).  Stationary kernels, one process.  Z is fixed per evaluation and may be replaced
-    between evaluations (``set_Z``: the warm-up of ``sgp_hmc.train_sgp_hmc`` optimises it)."""
+    between evaluations (``set_Z``: the warm-up of ``sgp_hmc.train_sgp_hmc`` optimises it).
 
-    def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None):
+    ``likelihood``: "gaussian" (the above), or one of the non-conjugate likelihoods SGPMC exists for -- "bernoulli" (probit link),
+    "bernoulli_logit" (labels {0, 1} or {-1, +1}) and "poisson" (log link, non-negative integer counts).  [UPSTREAM] GPflow's
+    ``SGPMC.log_likelihood_lower_bound`` as recalled: ``conditional(..., q_sqrt=None, white=True)`` then
+    ``likelihood.variational_expectations``.  They have no noise entry: q = [x_var | x_ls (d) | v (M)], ndim = d + 1 + M, the priors
+    and transforms of the remaining entries unchanged.  One evaluation is ``kuu`` -> ``kuu_factor`` -> ``sgpmc_lik_rows`` ->
+    ``sgpmc_lik_tail`` -> ``suffstats_bwd_factored(t_in = diag(dv) T, y = dmu, Cw = -2 I, s2 = 1, bbar = L^-T v)`` -> ``kuu_bwd``
+    (include/sgp.h states the density, its adjoints and why pass 2 needs no new kernel), again with one device-to-host copy: the
+    diagonal term of dF/d variance, sum_n dv_n, comes back in that copy and is added on the host, where pass 2's ``kappabar`` argument
+    would have needed it before the launch."""
+
+    LIKELIHOODS = ("gaussian", "bernoulli", "bernoulli_logit", "poisson")
+
+    def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None, likelihood="gaussian"):
         from .core import _world
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("SgpmcTarget takes the likelihoods %s (got %r)" % (", ".join(self.LIKELIHOODS), likelihood))
         if kernel not in ("rbf", "matern32", "matern52"):
             raise ValueError("SgpmcTarget takes the stationary kernels 'rbf', 'matern32', 'matern52' (got %r): composite kernels are "
                              "not supported" % (kernel,))
@@ -358,10 +372,23 @@ class SgpmcTarget:
         self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
         if self.X.shape[0] != self.y.shape[0]:
             raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
+        self.likelihood = likelihood
+        if likelihood in ("bernoulli", "bernoulli_logit"):   # {0, 1} or {-1, +1} labels -> {-1, +1}, on the host
+            yh = self.y.detach().to("cpu")
+            if not bool(((yh == 0.0) | (yh == 1.0) | (yh == -1.0)).all()) or (bool((yh == 0.0).any()) and bool((yh == -1.0).any())):
+                raise ValueError("Bernoulli labels must be {0, 1} or {-1, +1}")
+            if bool((yh == 0.0).any()):
+                self.y = (2.0 * yh - 1.0).to(engine.device).contiguous()
+        elif likelihood == "poisson":
+            yh = self.y.detach().to("cpu")
+            if not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
+                raise ValueError("Poisson counts must be non-negative integers")
+        self.n_theta = self.X.shape[1] + (2 if likelihood == "gaussian" else 1)   # [x_var | x_ls (d) | x_noise (Gaussian only)]
         self.kernel = kernel
         self.jitter = float(jitter)
         self.d = int(self.X.shape[1])
         self.N = int(self.X.shape[0])
+        self._cw_keep = None
         self.whitened_rows_min_work = WHITENED_ROWS_MIN_WORK
         self.last_pass1 = None   # "suffstats_whitened" / "suffstats_whitened_rows": which pass 1 the last evaluation ran
         self.n_evals = 0
@@ -376,19 +403,24 @@ class SgpmcTarget:
             raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
         self.Z = Z
         self.M = int(Z.shape[0])
-        self.ndim = self.d + 2 + self.M
+        self.ndim = self.n_theta + self.M
 
     def start(self):
         """GPflow's defaults as the reference sets them (models/sgp_hmc.py:36): variance log(2)^2, lengthscales log 2, likelihood
         variance 1, v = 0."""
         ln2 = math.log(2.0)
-        return [_softplus_inv(ln2 * ln2)] + [_softplus_inv(ln2)] * self.d + [_softplus_inv(1.0 - _SGPMC_NOISE_FLOOR)] + [0.0] * self.M
+        noise = [_softplus_inv(1.0 - _SGPMC_NOISE_FLOOR)] if self.likelihood == "gaussian" else []
+        return [_softplus_inv(ln2 * ln2)] + [_softplus_inv(ln2)] * self.d + noise + [0.0] * self.M
 
     def constrain(self, q):
+        """The constrained values of a position; ``noise_variance`` only with the Gaussian likelihood."""
         x = as_floats(q)
         d = self.d
-        return {"variance": _softplus(x[0]), "lengthscales": [_softplus(t) for t in x[1:1 + d]],
-                "noise_variance": _SGPMC_NOISE_FLOOR + _softplus(x[1 + d]), "V": np.asarray(x[2 + d:], dtype=np.float64)}
+        c = {"variance": _softplus(x[0]), "lengthscales": [_softplus(t) for t in x[1:1 + d]]}
+        if self.likelihood == "gaussian":
+            c["noise_variance"] = _SGPMC_NOISE_FLOOR + _softplus(x[1 + d])
+        c["V"] = np.asarray(x[self.n_theta:], dtype=np.float64)
+        return c
 
     def _t_for(self):
         e = self.engine
@@ -399,42 +431,73 @@ class SgpmcTarget:
             self._t_keep = e.kfu_buffer(self.N, self.M)
         return self._t_keep
 
-    def _eval(self, q, want_grad, want_gz=False):
-        x = as_floats(q)
-        d, M, e = self.d, self.M, self.engine
-        if len(x) != self.ndim:
-            raise ValueError("the position has %d entries, expected d + 2 + M = %d" % (len(x), self.ndim))
-        bad = (-math.inf, [0.0] * self.ndim if want_grad else None, None)
-        if not all(math.isfinite(t) for t in x) or not all(abs(t) < 700.0 for t in x[:d + 2]):
-            return bad
-        sf2, ls, s2 = _softplus(x[0]), [_softplus(t) for t in x[1:1 + d]], _SGPMC_NOISE_FLOOR + _softplus(x[1 + d])
-        if not (sf2 > 0.0 and all(t > 0.0 for t in ls)):   # softplus underflowed: outside the representable range
-            return bad
-        self.n_evals += 1
-        ng = d + 1 + (M * d if want_gz else 0)
-        extra = ng + M if want_grad else 0
-        result = e.result_buffer(extra)
-        buf = result[0]
-        head = buf.numel() - extra
-        Z = self.Z
-        Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
-        linv, _ = e.kuu_factor(Kuu, info=result[2])   # the evaluation's status word is the K_uu status: the tail factors nothing
+    def _cw(self):
+        """-2 I (M x M): the whitened core that turns the factored pass 2 into the N-side gradient of a non-conjugate likelihood."""
+        if self._cw_keep is None or self._cw_keep.shape[0] != self.M:
+            self._cw_keep = (-2.0 * torch.eye(self.M, dtype=torch.float64)).to(self.engine.device).contiguous()
+        return self._cw_keep
+
+    def _chain_gaussian(self, ls, sf2, s2, v, linv, result, vbar_kw, g, want_grad, want_gz):
+        """Pass 1 over the whitened statistics, the Gaussian tail and (``want_grad``) the factored pass 2 into ``g``; returns Kuubar."""
+        e, Z = self.engine, self.Z
         t_keep = None
-        if whitened_rows_layout(e, self.kernel, self.N, M, self.whitened_rows_min_work):
+        if whitened_rows_layout(e, self.kernel, self.N, self.M, self.whitened_rows_min_work):
             t_keep = self._t_for() if want_grad else None
             packed = e.suffstats_whitened_rows(self.X, self.y, Z, ls, sf2, linv, self.kernel, t_out=t_keep)
             self.last_pass1 = "suffstats_whitened_rows"
         else:
             packed = e.suffstats_whitened(self.X, self.y, Z, ls, sf2, linv, self.kernel)
             self.last_pass1 = "suffstats_whitened"
-        v = torch.tensor(x[2 + d:], dtype=torch.float64).to(e.device)
-        res = e.sgpmc_tail(packed, v, s2, self.N, linv, with_adjoints=want_grad, result=result,
-                           **({"vbar_out": buf[head + ng:]} if want_grad else {}))
+        res = e.sgpmc_tail(packed, v, s2, self.N, linv, with_adjoints=want_grad, result=result, **vbar_kw)
+        if not want_grad:
+            return None
+        e.suffstats_bwd_factored(self.X, self.y, Z, ls, sf2, linv, res["Cw"], s2, res["bbar"], -1.0 / (2.0 * s2), self.kernel,
+                                 want_gz=want_gz, out=g, **({"t_in": t_keep} if t_keep is not None else {}))
+        return res["Kuubar"]
+
+    def _chain_lik(self, ls, sf2, s2, v, linv, result, vbar_kw, g, want_grad, want_gz):
+        """The same for a non-conjugate likelihood: the row pass over T, its tail, and pass 2 on T_in = diag(dv) T with y := dmu,
+        Cw := -2 I, s2 := 1, bbar := L^-T v (kappabar = 0: sum_n dv_n is added on the host, see ``_eval``)."""
+        e, Z = self.engine, self.Z
+        t_keep = self._t_for()
+        rows = e.sgpmc_lik_rows(self.X, self.y, Z, ls, sf2, 1.0, v, linv, t_keep, self.kernel, self.likelihood, want_adjoints=want_grad)
+        self.last_pass1 = "sgpmc_lik_rows"
+        res = e.sgpmc_lik_tail(rows, v, self.N, linv, with_adjoints=want_grad, result=result, **vbar_kw)
+        if not want_grad:
+            return None
+        e.suffstats_bwd_factored(self.X, rows["dmu"], Z, ls, sf2, linv, self._cw(), 1.0, res["bbar"], 0.0, self.kernel,
+                                 want_gz=want_gz, out=g, t_in=t_keep)
+        return res["Kuubar"]
+
+    def _eval(self, q, want_grad, want_gz=False):
+        x = as_floats(q)
+        d, M, e, nt = self.d, self.M, self.engine, self.n_theta
+        gaussian = self.likelihood == "gaussian"
+        if len(x) != self.ndim:
+            raise ValueError("the position has %d entries, expected %d theta + M = %d" % (len(x), nt, self.ndim))
+        bad = (-math.inf, [0.0] * self.ndim if want_grad else None, None)
+        if not all(math.isfinite(t) for t in x) or not all(abs(t) < 700.0 for t in x[:nt]):
+            return bad
+        sf2, ls = _softplus(x[0]), [_softplus(t) for t in x[1:1 + d]]
+        s2 = _SGPMC_NOISE_FLOOR + _softplus(x[1 + d]) if gaussian else None
+        if not (sf2 > 0.0 and all(t > 0.0 for t in ls)):   # softplus underflowed: outside the representable range
+            return bad
+        if not gaussian and self._t_for() is None:
+            raise ValueError("the engine has no kfu_buffer: SgpmcTarget(likelihood=%r) needs the caller-owned T" % (self.likelihood,))
+        self.n_evals += 1
+        ng = d + 1 + (M * d if want_gz else 0)
+        extra = ng + M if want_grad else 0
+        result = e.result_buffer(extra)
+        buf = result[0]
+        head = buf.numel() - extra
+        Kuu = e.kuu(self.Z, ls, sf2, self.jitter, self.kernel)
+        linv, _ = e.kuu_factor(Kuu, info=result[2])   # the evaluation's status word is the K_uu status: the tails factor nothing
+        v = torch.tensor(x[nt:], dtype=torch.float64).to(e.device)
+        g = buf[head:head + ng] if want_grad else None
+        chain = self._chain_gaussian if gaussian else self._chain_lik
+        Kuubar = chain(ls, sf2, s2, v, linv, result, {"vbar_out": buf[head + ng:]} if want_grad else {}, g, want_grad, want_gz)
         if want_grad:
-            g = buf[head:head + ng]
-            e.suffstats_bwd_factored(self.X, self.y, Z, ls, sf2, linv, res["Cw"], s2, res["bbar"], -1.0 / (2.0 * s2), self.kernel,
-                                     want_gz=want_gz, out=g, **({"t_in": t_keep} if t_keep is not None else {}))
-            e.kuu_bwd(Z, ls, sf2, res["Kuubar"], g, self.kernel, want_gz=want_gz)
+            e.kuu_bwd(self.Z, ls, sf2, Kuubar, g, self.kernel, want_gz=want_gz)
         host = buf.detach().to("cpu")   # the one host round trip
         o, info = e.read_result(host)
         if info < 0:
@@ -443,8 +506,8 @@ class SgpmcTarget:
         if info != 0 or not math.isfinite(F):
             return bad
         # priors at the constrained values + log sigmoid(x) for the transform
-        cons = [sf2] + ls + [s2]
-        sig = [_sigmoid(t) for t in x[:d + 2]]
+        cons = [sf2] + ls + ([s2] if gaussian else [])
+        sig = [_sigmoid(t) for t in x[:nt]]
         if not all(s > 0.0 for s in sig):
             return bad
         logp = F + sum(math.log(c) - c for c in cons) + sum(math.log(s) for s in sig)
@@ -452,8 +515,10 @@ class SgpmcTarget:
             return logp, None, None
         hl = host.tolist()
         gh = hl[head:head + d + 1]
-        dF = [gh[d]] + gh[:d] + [float(o[3])]   # dF/d variance, dF/d lengthscales, dF/d s2 (SGP_SGPMC_OUT_S2BAR)
-        grad = [(dF[k] + 1.0 / cons[k] - 1.0) * sig[k] + (1.0 - sig[k]) for k in range(d + 2)] + hl[head + ng:head + ng + M]
+        # dF/d variance, dF/d lengthscales and, Gaussian, dF/d s2 (SGP_SGPMC_OUT_S2BAR).  Non-conjugate: + sum_n dv_n = N out[4] on
+        # dF/d variance (k(x_n, x_n) = variance), which pass 2's host scalar kappabar could not carry without a second host copy
+        dF = [gh[d]] + gh[:d] + [float(o[3])] if gaussian else [gh[d] + float(o[4]) * self.N] + gh[:d]
+        grad = [(dF[k] + 1.0 / cons[k] - 1.0) * sig[k] + (1.0 - sig[k]) for k in range(nt)] + hl[head + ng:head + ng + M]
         if not all(math.isfinite(t) for t in grad):
             return bad
         gz = buf[head + d + 1:head + ng].reshape(M, d) if want_gz else None

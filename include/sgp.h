@@ -503,6 +503,49 @@ int sgp_sgpmc_from_whitened_stats(const double* W, const double* u, const double
                                   double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
                                   sgp_stream_t stream);
 
+/* ---- SGPMC with a non-conjugate likelihood --------------------------------------------------------------------------------------
+ * [UPSTREAM] GPflow's SGPMC.log_likelihood_lower_bound -- conditional(..., q_sqrt=None, white=True), then
+ * likelihood.variational_expectations -- as recalled: GPflow is not installed here and nothing was checked against it.  With
+ * a_n = L^-1 k_u(x_n) (= sf2 T_n for the unit-amplitude T = K'_fu L^-T of sgp_suffstats_fwd_whitened_rows):
+ *   mu_n = a_n.v     var_n = sf2 - |a_n|^2     ell_n = E_{N(mu_n, var_n)} log p(y_n | f)
+ *   F(v, theta) = sum_n ell_n - 1/2 v.v - M/2 log(2 pi)
+ * and, with dmu_n = d ell_n / d mu_n, dv_n = d ell_n / d var_n,
+ *   g = sum_n dmu_n a_n (M)     G = sum_n dv_n a_n a_n^T (M x M)     vbar = g - v     bbar = w = L^-T v
+ *   Kuubar = L^-T (G - sym(low(v g^T))) L^-1                        low(), sym() as for sgp_sgpmc_from_whitened_stats
+ *   Kfubar row n = dmu_n w^T - 2 dv_n (sf2 T_n) L^-1                dF / d k(x_n, x_n) = dv_n
+ * likelihood_id: the SGP_LIK_* of the SVGP section below (all log-concave, so dv_n <= 0 and G = -S^T S, S_n = sqrt(-dv_n) a_n^T: the
+ * contraction of pass 1 on a row-scaled T).  A var_n below 2^-40 sf2 (a datum on an inducing input) is raised to it and its dv_n is 0;
+ * so is a dv_n that comes out positive (rounding noise of a quadrature whose nodes are all saturated).
+ * The N-side gradient needs no kernel of its own: sgp_suffstats_bwd_factored_ex forms Kfubar = sf2 T_in (Cw / s2) L^-1 + y bbar^T, so
+ * T_in = diag(dv) T (what T_out holds on return), y := dmu, bbar := w, Cw := -2 I, s2 := 1 is exactly the row above, and kappabar :=
+ * (sum_n dv_n) / N adds the diagonal term to dF/dsf2; sgp_kuu_bwd follows with Kuubar.
+ *
+ * sgp_sgpmc_lik_rows: prologue, kernel assembly and T = K'_fu L^-T as sgp_suffstats_fwd_whitened_rows (stationary kernels only:
+ * SGP_KERNEL_COMPOSITE -> SGP_ERR_ARG), then one pass over T for the moments and the likelihood.  T_out (DEVICE, sgp_kfu_len(N, M)
+ * doubles, required) is the caller's and holds the whole shard: a shard whose K'_fu exceeds the library's budget of one super-chunk
+ * is refused (the workspace query returns 0, the call SGP_ERR_WORKSPACE).
+ *   out (DEVICE, SGP_SGPMC_LIK_OUT_LEN) = [sum_n ell_n | d sum ell / d s2 (Gaussian; else 0) | sum_n dv_n]
+ *   dmu, dv (DEVICE, N doubles)           the per-datum derivatives
+ *   want_adjoints != 0: also g (M), G (M x M, ld M), and T_out = diag(dv) T with zero padding; 0: T_out = T, nothing is launched
+ *   behind the row pass, G and g may be NULL.
+ * s2 is read by SGP_LIK_GAUSSIAN alone (s2 <= 0 -> SGP_ERR_ARG there).  Every sum runs in a fixed order: the same inputs give the same
+ * bits, whatever the workspace held before.  Non-finite intermediate values (exp overflow under SGP_LIK_POISSON_LOG) reach out[0] as
+ * -inf / nan and never an address.  The status of K_uu is sgp_kuu_factor(_ex)'s.
+ * sgp_sgpmc_lik_tail: from rows_out (the `out` above), G, g, v and kuu_linv the value
+ *   out[SGP_SGPMC_OUT_F] = F, _DATA = sum ell, _PRIOR = -1/2 v.v - M/2 log(2 pi), _S2BAR = d sum ell / d s2, _KAPPABAR = (sum dv) / N
+ * and with_adjoints != 0: vbar, bbar (M doubles), Kuubar (M x M, ld M).  The kernels of sgp_sgpmc_from_whitened_stats, four launches
+ * (two without the adjoints, which need none of G, g, vbar, bbar, Kuubar, kuu_linv).                                               */
+#define SGP_SGPMC_LIK_OUT_LEN 3
+size_t sgp_sgpmc_lik_rows_workspace_bytes(int64_t N, int M, int d);
+int sgp_sgpmc_lik_rows(const double* X, int64_t ldx, const double* y, const double* Z, int64_t ldz, const double* inv_ls, double sf2,
+                       double s2, const double* v, int64_t N, int M, int d, int kernel_id, int likelihood_id, const double* kuu_linv,
+                       int want_adjoints, double* out, double* G, double* g, double* dmu, double* dv, double* T_out, void* ws,
+                       size_t ws_bytes, sgp_stream_t stream);
+size_t sgp_sgpmc_lik_workspace_bytes(int M);
+int sgp_sgpmc_lik_tail(const double* rows_out, const double* G, const double* g, const double* v, int64_t N, int M, int with_adjoints,
+                       double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
+                       sgp_stream_t stream);
+
 /* ---- single-launch evaluation for small problems (M <= 128; stationary kernels d <= 24, composite d <= 8) -------------------------
  * The size class of the reference's own HMC runs (models/bayesian_sgpr_hmc.py:58-80,144-157: N ~ 250-1300, M = 100).
  * ONE cooperative kernel launch evaluates the bound and its gradient in the PyMC3 op order (A = L^-1 K_uf by blocked
@@ -670,10 +713,13 @@ int sgp_predict(const double* Xs, int64_t ldxs, int64_t T,
  * a Cholesky variational distribution (models/svgp.py:37,46,88-127), and loss.backward() through it.
  *   m[M], LS[M*M] (lower triangle used, ld M): q(u) = N(m, LS LS^T) in the whitened parametrisation
  *   out[0] = mean_b E_q log p(y_b|f_b) - KL / N_total ; out[1] = sum_b E_q log p ; out[2] = KL
- *   likelihood_id: SGP_LIK_GAUSSIAN (noise s2) or SGP_LIK_BERNOULLI_PROBIT (y in {-1,+1}, 20-point Gauss-Hermite)
+ *   likelihood_id: SGP_LIK_GAUSSIAN (noise s2), SGP_LIK_BERNOULLI_PROBIT / _LOGIT (y in {-1,+1}, 20-point Gauss-Hermite) or
+ *                  SGP_LIK_POISSON_LOG (counts y >= 0 with a log link, closed form); s2 is read by the Gaussian alone
  *   with_grads: d out[0] / d{m, LS (lower), Z, lengthscale_j, sf2, s2}; info as for the collapsed bound (1..M).  */
 #define SGP_LIK_GAUSSIAN 0
 #define SGP_LIK_BERNOULLI_PROBIT 1
+#define SGP_LIK_BERNOULLI_LOGIT 2
+#define SGP_LIK_POISSON_LOG 3
 size_t sgp_svgp_workspace_bytes(int64_t B, int M, int d);
 int sgp_svgp_elbo(const double* Xb, int64_t ldx, const double* yb, int64_t B,
                   const double* Z, int64_t ldz, const double* inv_ls, double sf2, double s2, double jitter,
