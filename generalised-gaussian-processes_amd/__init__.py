@@ -4,8 +4,8 @@ The directory name follows the project naming (``generalised-gaussian-processes_
 valid Python identifier: import it through the repo-root shim ``ggp_amd`` (``import ggp_amd``).
 """
 from ._lib import KERNEL_IDS, SgpLibraryError, SgpStatusError, load_library  # noqa: F401
-from .composite import (CO2_LOG_PRIOR_SD, CompositeBayesianSparseGPR_HMC, CompositeHmcTarget, CompositeKernel, Factor,  # noqa: F401
-                        co2_kernel)
+from .composite import (CO2_LOG_PRIOR_SD, CO2_SGPMC_PRIORS, CompositeBayesianSparseGPR_HMC, CompositeHmcTarget, CompositeKernel,  # noqa: F401
+                        CompositeSgpmcTarget, Factor, co2_kernel, co2_sgpmc_kernel)
 from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
 from . import datasets, experiment_tools  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
@@ -14,7 +14,8 @@ from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_dev
 from .metrics import negative_log_predictive_mixture_density, nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
-from .sgp_hmc import SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments, predict_sgpmc, train_sgp_hmc  # noqa: F401
+from .sgp_hmc import (CompositeSgpmcModel, SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments,  # noqa: F401
+                      predict_sgpmc, train_sgp_hmc, train_sgp_hmc_composite)
 from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget  # noqa: F401
 
 

@@ -150,6 +150,12 @@ PROTOTYPES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_sgpmc_lik_workspace_bytes": (_sz, [_i32]),
     "sgp_sgpmc_lik_tail": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # ... with a composite kernel, a white-noise term and a mean function
+    "sgp_sgpmc_comp_rows_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_sgpmc_comp_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _dp, _dbl, _dbl, _vp, _i64, _i32, _i32, _i32, _vp, _i32,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_sgpmc_comp_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_sgpmc_comp_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "sgp_suffstats_bwd_factored_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "sgp_suffstats_bwd_factored": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _dbl, _vp, _vp, _dbl, _vp, _dbl, _i64, _i32, _i32, _i32,
                                           _vp, _vp, _vp, _vp, _sz, _vp]),

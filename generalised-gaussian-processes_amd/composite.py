@@ -21,9 +21,10 @@ import numpy as np
 import torch
 
 from ._lib import COMP_LEN
-from .core import CollapsedBound, few_host_threads
+from .core import CollapsedBound, SgpTimeoutError, few_host_threads
 from .hmc import next_seed, sample_nuts, sample_nuts_device, trace_summary
-from .targets import as_floats, device_sampler_ok, in_range, single_launch_eval, single_launch_ok
+from .targets import (_SGPMC_NOISE_FLOOR, SgpmcTarget, _sigmoid, _softplus, _softplus_inv, as_floats, device_sampler_ok, in_range,
+                      single_launch_eval, single_launch_ok)
 
 EXPQUAD, MATERN32, MATERN52, RATQUAD, PERIODIC = 0, 1, 2, 3, 4
 _FACTOR_IDS = {"expquad": EXPQUAD, "rbf": EXPQUAD, "matern32": MATERN32, "matern52": MATERN52, "ratquad": RATQUAD,
@@ -201,6 +202,270 @@ class CompositeHmcTarget:
 
     def logp(self, theta):
         return self.logp_and_grad(theta)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SGPMC + HMC with a composite kernel, white noise and a linear mean function (the reference's experiments/co2_sgpmc.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def co2_sgpmc_kernel() -> CompositeKernel:
+    """The covariance of experiments/co2_sgpmc.py:66-73 without its White term (``CompositeSgpmcTarget(white=...)`` carries that):
+    Periodic(SquaredExponential, period 1, fixed) * Matern52 with ONE variance (the Matern's is frozen at 1, :73) + RationalQuadratic
+    + SquaredExponential(variance log(2)^2) + Matern52, every other value at GPflow's default 1.
+    [UPSTREAM] GPflow's ``Periodic(base_kernel=SquaredExponential)`` is taken to be variance * exp(-1/2 sum_j sin^2(pi r_j / period) /
+    lengthscale^2) -- its docstring as recalled, equal to SGP_FAC_PERIODIC; GPflow is not installed and nothing was checked against it."""
+    return CompositeKernel([
+        (1.0, [Factor("periodic", 1.0, 1.0, fixed_aux=True), Factor("matern52", 1.0)]),
+        (1.0, [Factor("ratquad", 1.0, 1.0)]),
+        (math.log(2.0), [Factor("expquad", 1.0)]),
+        (1.0, [Factor("matern52", 1.0)]),
+    ])
+
+
+# experiments/co2_sgpmc.py:61-90,109, under the names of ``CompositeSgpmcTarget.names`` for ``co2_sgpmc_kernel()``
+CO2_SGPMC_PRIORS = {
+    "variance_0": ("halfnormal", 2.0), "lengthscale_0_0": ("gamma", 4.0, 3.0), "lengthscale_0_1": ("gamma", 10.0, 0.075),
+    "variance_1": ("halfnormal", 0.5), "lengthscale_1_0": ("gamma", 2.0, 0.75), "alpha_1_0": ("gamma", 5.0, 2.0),
+    "variance_2": ("halfnormal", 2.0), "lengthscale_2_0": ("gamma", 4.0, 0.1),
+    "variance_3": ("halfnormal", 0.5), "lengthscale_3_0": ("gamma", 2.0, 4.0),
+    "white": ("halfnormal", 0.25), "mean_A": ("normal", 0.0, 3.0), "mean_b": ("normal", 0.0, 3.0), "noise_variance": ("gamma", 2.0, 1.0),
+}
+
+
+def _log_prior(spec, c):
+    """(log density, its derivative) of one prior at the value c: ("gamma", concentration, rate) | ("halfnormal", scale) |
+    ("normal", mean, sd)."""
+    kind = spec[0]
+    if kind == "gamma":
+        a, b = float(spec[1]), float(spec[2])
+        return a * math.log(b) - math.lgamma(a) + (a - 1.0) * math.log(c) - b * c, (a - 1.0) / c - b
+    if kind == "halfnormal":
+        s = float(spec[1])
+        return 0.5 * math.log(2.0 / math.pi) - math.log(s) - 0.5 * (c / s) ** 2, -c / (s * s)
+    if kind == "normal":
+        m, s = float(spec[1]), float(spec[2])
+        return -0.5 * math.log(2.0 * math.pi) - math.log(s) - 0.5 * ((c - m) / s) ** 2, -(c - m) / (s * s)
+    raise ValueError("unknown prior %r: 'gamma', 'halfnormal' or 'normal'" % (kind,))
+
+
+class CompositeSgpmcTarget:
+    """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values of GPflow's ``SGPMC`` with a
+    sum-of-products kernel, an optional White term and an optional linear mean function -- the model of experiments/co2_sgpmc.py.
+
+    q, unconstrained, in this order (``names``): per term of ``kernel`` ``variance_t`` (the block's amp2 slot: GPflow's parameter, not
+    the amplitude sd), per factor ``lengthscale_t_f`` and each free ``alpha_t_f`` (ratquad) / ``period_t_f`` (an unfixed period);
+    ``white`` (when ``white`` is not None: its start value); ``noise_variance`` (Gaussian likelihood only, floor 1e-6); ``mean_A`` (d)
+    and ``mean_b`` (``mean="linear"``: m(x) = x.A + b); ``V`` (M).  Positive entries go through softplus with log sigmoid(x) added for
+    the transform, as ``SgpmcTarget`` does; the mean coefficients are unconstrained.  ``priors``: name -> ("gamma", concentration,
+    rate) | ("halfnormal", scale) | ("normal", mean, sd) on the constrained value; a name without an entry contributes nothing
+    ([UPSTREAM] GPflow's ``log_prior_density`` as recalled).  V ~ N(0, I).
+
+    The density F(v, theta) and its adjoints are stated in include/sgp.h (sgp_sgpmc_comp_rows).  One evaluation is
+    ``kuu(jitter + white)`` -> ``kuu_factor`` -> ``sgpmc_comp_rows`` -> ``sgpmc_lik_tail`` -> ``sgpmc_comp_bwd`` -> ``kuu_bwd``, with one
+    result buffer and one device-to-host copy (tr(Kuubar) for dF/dwhite and the two sums of the mean function ride in it); transforms,
+    priors and the chain rule run on the host.  A non-zero ``kuu_factor`` status or a non-finite value gives (-inf, zeros); a device
+    time-out raises ``SgpTimeoutError``.  Z is fixed per evaluation (``set_Z`` replaces it); there is no dF/dZ.  One process."""
+
+    LIKELIHOODS = SgpmcTarget.LIKELIHOODS
+
+    def __init__(self, X, y, Z, kernel: CompositeKernel, priors=None, white=None, mean=None, likelihood="gaussian", jitter=1e-4,
+                 engine=None):
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("CompositeSgpmcTarget takes the likelihoods %s (got %r)" % (", ".join(self.LIKELIHOODS), likelihood))
+        if mean not in (None, "linear"):
+            raise ValueError("mean is None or 'linear' (got %r)" % (mean,))
+        if white is not None and not float(white) > 0.0:
+            raise ValueError("white is None (no White term) or its positive start value")
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine(X.device if X.is_cuda else None)
+        self.engine = engine
+        if X.dim() == 1:
+            X = X[:, None]
+        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
+        yh = y.detach().to(dtype=torch.float64, device="cpu").reshape(-1)
+        if self.X.shape[0] != yh.shape[0]:
+            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], yh.shape[0]))
+        if likelihood in ("bernoulli", "bernoulli_logit"):   # {0, 1} or {-1, +1} labels -> {-1, +1}
+            if not bool(((yh == 0.0) | (yh == 1.0) | (yh == -1.0)).all()) or (bool((yh == 0.0).any()) and bool((yh == -1.0).any())):
+                raise ValueError("Bernoulli labels must be {0, 1} or {-1, +1}")
+            if bool((yh == 0.0).any()):
+                yh = 2.0 * yh - 1.0
+        elif likelihood == "poisson" and not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
+            raise ValueError("Poisson counts must be non-negative integers")
+        self.y = yh.to(engine.device).contiguous()
+        self.likelihood, self.kernel, self.jitter, self.mean = likelihood, kernel, float(jitter), mean
+        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+        self.priors = dict(priors or {})
+        self._structure = kernel.block()
+        # the theta entries: (name, role, block slot or coefficient index, start value); roles amp / ls / aux / white / noise are positive
+        ent = []
+        for (pname, slot, role), val in zip(kernel.free_parameters(), kernel.values()):
+            t_f = pname.split("_", 1)[1]
+            if role == "amp":
+                ent.append(("variance_" + t_f, role, slot, val * val))
+            elif role == "ls":
+                ent.append(("lengthscale_" + t_f, role, slot, val))
+            else:
+                ent.append((("alpha_" if int(self._structure[slot - 2]) == RATQUAD else "period_") + t_f, role, slot, val))
+        if white is not None:
+            ent.append(("white", "white", -1, float(white)))
+        if likelihood == "gaussian":
+            ent.append(("noise_variance", "noise", -1, 1.0))
+        if mean == "linear":
+            ent += [("mean_A", "A", j, 1.0) for j in range(self.d)] + [("mean_b", "b", 0, 0.0)]
+        self._entries = ent
+        self.n_theta = len(ent)
+        for name in self.priors:
+            if name not in {e[0] for e in ent}:
+                raise ValueError("a prior is given for %r, which this target does not sample (%s)" % (name, ", ".join(self.names)))
+            _log_prior(self.priors[name], 1.0)
+        self.n_evals = 0
+        self._t_keep = None
+        self.set_Z(Z)
+
+    @property
+    def names(self):
+        """The theta entries in the order of q (``mean_A`` once per input dimension), without ``V``."""
+        return [e[0] for e in self._entries]
+
+    def set_Z(self, Z):
+        if Z.dim() == 1:
+            Z = Z[:, None]
+        Z = Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
+        if Z.shape[1] != self.d:
+            raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
+        self.Z = Z
+        self.M = int(Z.shape[0])
+        self.ndim = self.n_theta + self.M
+
+    def start(self):
+        """[UPSTREAM] GPflow's defaults as recalled: variances, lengthscales, alpha, white and the likelihood variance 1, A = 1, b = 0,
+        V = 0 -- with ``kernel``'s own values (``co2_sgpmc_kernel()``: variance log(2)^2 on the trend) and ``white``'s start value."""
+        out = []
+        for _, role, _, val in self._entries:
+            out.append(val if role in ("A", "b") else _softplus_inv(val - (_SGPMC_NOISE_FLOOR if role == "noise" else 0.0)))
+        return out + [0.0] * self.M
+
+    def unpack(self, q):
+        """(block, white, noise variance or None, A list or None, b, constrained theta list) of a position."""
+        x = as_floats(q)
+        block, white, s2, A, b, cons = list(self._structure), 0.0, None, None, 0.0, []
+        for (_, role, idx, _), t in zip(self._entries, x):
+            if role in ("A", "b"):
+                c = t
+            else:
+                c = _softplus(t) + (_SGPMC_NOISE_FLOOR if role == "noise" else 0.0)
+            cons.append(c)
+            if role in ("amp", "ls", "aux"):
+                block[idx] = c
+            elif role == "white":
+                white = c
+            elif role == "noise":
+                s2 = c
+            elif role == "A":
+                A = (A or []) + [c]
+            else:
+                b = c
+        return block, white, s2, A, b, cons
+
+    def constrain(self, q):
+        """The constrained values of a position under ``names`` (``mean_A`` as an array), ``V``, and ``kernel`` (a ``CompositeKernel``)."""
+        x = as_floats(q)
+        block, _, _, A, _, cons = self.unpack(x)
+        c = {name: v for (name, role, _, _), v in zip(self._entries, cons) if role != "A"}
+        if A is not None:
+            c["mean_A"] = np.asarray(A, dtype=np.float64)
+        c["V"] = np.asarray(x[self.n_theta:], dtype=np.float64)
+        c["kernel"] = self.kernel.with_values([math.sqrt(block[s]) if r == "amp" else block[s] for _, s, r in self.kernel.free_parameters()])
+        return c
+
+    def _t_for(self):
+        if self._t_keep is None or self._t_keep.numel() < ((max(self.N, 1) + 255) // 256 * 256) * ((self.M + 127) // 128 * 128):
+            self._t_keep = self.engine.kfu_buffer(self.N, self.M)
+        return self._t_keep
+
+    def _eval(self, q, want_grad):
+        x = as_floats(q)
+        d, M, N, e, nt = self.d, self.M, self.N, self.engine, self.n_theta
+        if len(x) != self.ndim:
+            raise ValueError("the position has %d entries, expected %d theta + M = %d" % (len(x), nt, self.ndim))
+        bad = (-math.inf, [0.0] * self.ndim if want_grad else None)
+        positive = [role not in ("A", "b") for _, role, _, _ in self._entries]
+        if not all(math.isfinite(t) for t in x) or not all(abs(t) < 700.0 for t, p in zip(x, positive) if p):
+            return bad
+        block, white, s2, A, b, cons = self.unpack(x)
+        if not all(c > 0.0 for c, p in zip(cons, positive) if p):   # softplus underflowed: outside the representable range
+            return bad
+        self.n_evals += 1
+        linear = A is not None
+        # extras of the result buffer: [dF/d block (COMP_LEN) + kuu_bwd's amplitude slot | vbar (M) | tr Kuubar | sum dmu x (d) | sum dmu].
+        # The amplitude slot exists because kuu_bwd's layout has it; the composite path never writes it and nothing here reads it: it
+        # holds whatever torch.empty left (clearing it would cost a launch per evaluation).
+        extra = COMP_LEN + 1 + M + 1 + d + 1 if want_grad else 0
+        result = e.result_buffer(extra)
+        buf = result[0]
+        head = buf.numel() - extra
+        Kuu = e.kuu(self.Z, block, 1.0, self.jitter + white, "composite")   # White is K_uu's diagonal and k(x, x) only
+        linv, _ = e.kuu_factor(Kuu, info=result[2])                         # the evaluation's status word is the K_uu status
+        up = torch.tensor(x[nt:] + (A + [b] if linear else []), dtype=torch.float64).to(e.device)
+        v = up[:M]
+        mean = torch.addmv(up[M + d:].expand(N), self.X, up[M:M + d]) if linear else None
+        t_keep = self._t_for()
+        rows = e.sgpmc_comp_rows(self.X, self.y, self.Z, block, white, s2 if s2 is not None else 1.0, v, linv, t_keep, self.likelihood,
+                                 mean=mean, want_adjoints=want_grad)
+        o_g, o_v, o_t = head, head + COMP_LEN + 1, head + COMP_LEN + 1 + M
+        res = e.sgpmc_lik_tail(rows, v, N, linv, with_adjoints=want_grad, result=result, **({"vbar_out": buf[o_v:o_t]} if want_grad else {}))
+        if want_grad:
+            g = buf[o_g:o_v]
+            e.sgpmc_comp_bwd(self.X, rows["dmu"], self.Z, block, t_keep, linv, res["bbar"], out=g)
+            e.kuu_bwd(self.Z, block, 1.0, res["Kuubar"], g, "composite")
+            torch.sum(torch.diagonal(res["Kuubar"]), dim=0, keepdim=True, out=buf[o_t:o_t + 1])
+            if linear:
+                torch.mv(self.X.t(), rows["dmu"], out=buf[o_t + 1:o_t + 1 + d])
+                torch.sum(rows["dmu"], dim=0, keepdim=True, out=buf[o_t + 1 + d:o_t + 2 + d])
+        host = buf.detach().to("cpu")   # the one host round trip
+        o, info = e.read_result(host)
+        if info < 0:
+            raise SgpTimeoutError()
+        F = float(o[0])
+        if info != 0 or not math.isfinite(F):
+            return bad
+        logp = F
+        pri = []
+        for (name, _, _, _), c, t, p in zip(self._entries, cons, x, positive):
+            lp, dlp = _log_prior(self.priors[name], c) if name in self.priors else (0.0, 0.0)
+            sg = _sigmoid(t) if p else 1.0
+            if not sg > 0.0:
+                return bad
+            logp += lp + (math.log(sg) if p else 0.0)
+            pri.append((dlp, sg))
+        if not want_grad:
+            return logp, None
+        hl = host.tolist()
+        gb, sdv, tr = hl[o_g:o_g + COMP_LEN], float(o[4]) * N, hl[o_t]
+        grad = []
+        for (_, role, idx, _), (dlp, sg), p in zip(self._entries, pri, positive):
+            if role == "amp":       # k(x_n, x_n) holds every amp2 slot: + sum_n dv_n (N out[4], as SgpmcTarget adds it)
+                dF = gb[idx] + sdv
+            elif role in ("ls", "aux"):
+                dF = gb[idx]
+            elif role == "white":
+                dF = tr + sdv
+            elif role == "noise":
+                dF = float(o[3])
+            else:
+                dF = hl[o_t + 1 + idx] if role == "A" else hl[o_t + 1 + d]
+            grad.append((dF + dlp) * sg + (1.0 - sg) if p else dF + dlp)
+        grad += hl[o_v:o_t]
+        if not all(math.isfinite(t) for t in grad):
+            return bad
+        return logp, grad
+
+    def logp(self, q):
+        return self._eval(q, False)[0]
+
+    def logp_and_grad(self, q):
+        return self._eval(q, True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,6 @@
 
 namespace sgp {
 
-constexpr int64_t COMP_CHUNK_ROWS = 65536;  // rows of K_fu materialised at a time
 constexpr int COMP_BLK_ROWS = 1024;         // rows one workgroup of the gradient kernel contracts
 
 // out[i][j] = k(a_i, b_j) for i < na, j < nb (+ jitter on i == j), zero in the padding; rows_p x cols_p, ld cols_p
@@ -66,6 +65,10 @@ static int grid_for_c(int64_t total, int cap = 4096) {
 void comp_kmatrix(const double* A, int64_t lda, int64_t na, const double* B, int64_t ldb, int nb, const CompSpec& cs, int d,
                   int64_t rows_p, int cols_p, double jitter, double* out, hipStream_t st) {
   comp_k_kernel<<<grid_for_c(rows_p * cols_p), 256, 0, st>>>(A, lda, B, ldb, cs, d, na, nb, rows_p, cols_p, jitter, out);
+}
+
+void comp_colsum(const double* K, int64_t ldk, const double* y, int64_t rows, int Mp, int accumulate, double* bp, hipStream_t st) {
+  comp_colsum_kernel<<<Mp / 64, 1024, 0, st>>>(K, ldk, y, rows, Mp, accumulate, bp);
 }
 
 static int64_t chunk_rows(int64_t N) {
@@ -323,6 +326,44 @@ int comp_suffstats_bwd_factored(const double* X, int64_t ldx, const double* y, c
                                 int M, int d, double* g_blk, double* g_Z, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!Linv || !Cw || !(s2 > 0.0)) return SGP_ERR_ARG;
   return comp_bwd_impl(X, ldx, y, Z, ldz, cs, nullptr, Linv, Cw, s2, bbar, kappabar, N, M, d, g_blk, g_Z, ws, ws_bytes, st);
+}
+
+// ---- the N-side gradient of SGPMC (sgp_sgpmc_comp_bwd): Kfubar = -2 T_in L^-1 + dmu w^T, one product per row chunk, then the
+// contraction above with yv := dmu, bb := w.  No K_fu is formed: comp_grad_kernel evaluates the derivatives from X and Z.
+size_t comp_sgpmc_bwd_workspace_bytes(int64_t N, int M) {
+  const GradGeom gg = grad_geom(N, M);
+  Carver c(nullptr);
+  c.take<double>((size_t)chunk_rows(N) * padded_m(M));
+  c.take<double>(grad_blocks_max(N, gg) * SGP_COMP_LEN);
+  return c.used();
+}
+
+int comp_sgpmc_bwd(const double* X, int64_t ldx, const double* dmu, const double* Z, int64_t ldz, const CompSpec& cs, const double* T_in,
+                   const double* Linv, const double* w, int64_t N, int M, int d, double* g_blk, void* ws, size_t ws_bytes,
+                   hipStream_t st) {
+  if (!ws || ws_bytes < comp_sgpmc_bwd_workspace_bytes(N, M)) return SGP_ERR_WORKSPACE;
+  const int Mp = padded_m(M);
+  const int64_t Rc = chunk_rows(N);
+  const GradGeom gg = grad_geom(N, M);
+  Carver c(ws);
+  double* Cc = c.take<double>((size_t)Rc * Mp);
+  double* gpp = c.take<double>(grad_blocks_max(N, gg) * SGP_COMP_LEN);
+  int64_t blk0 = 0;
+  // T_in is one contiguous row-major array, so the chunking here (chunk_rows(N), 64-row padding) need not be the one that wrote it
+  // (sgp_sgpmc_comp_rows: min(round_up(N, 256), COMP_CHUNK_ROWS)); both start their chunks at multiples of COMP_CHUNK_ROWS.
+  for (int64_t r0 = 0; r0 < N; r0 += Rc) {
+    const int64_t rn = (N - r0) < Rc ? (N - r0) : Rc;
+    GemmDesc g;  // Cc = -2 T_in L^-1   (T_in holds round_up(N, 256) rows: the 64-row padding of a chunk is inside it)
+    g.A = T_in + (size_t)r0 * Mp; g.lda = Mp; g.B = Linv; g.ldb = Mp; g.C = Cc; g.ldc = Mp;
+    g.m = (int)round_up64(rn, 64); g.n = Mp; g.k = Mp; g.alpha = -2.0;
+    gemm(g, st);
+    const int nb = (int)((rn + gg.blk_rows - 1) / gg.blk_rows);
+    comp_grad_kernel<<<nb, 256, 0, st>>>(X + r0 * ldx, ldx, dmu + r0, Z, ldz, cs, Cc, Mp, w, rn, M, d, blk0, gg.MC, gg.RL, gg.blk_rows,
+                                         gpp, nullptr);
+    blk0 += nb;
+  }
+  comp_grad_reduce_kernel<<<1, 256, 0, st>>>(gpp, nullptr, blk0, 0, M, d, cs, 0.0, 1.0, 0, g_blk, nullptr);
+  return check_launch();
 }
 
 size_t comp_kuu_bwd_workspace_bytes(int M, int d) {

@@ -11,6 +11,7 @@
 namespace sgp {
 
 constexpr int COMP_MAX_DIM = 8;  // input dimension the composite path accepts
+constexpr int64_t COMP_CHUNK_ROWS = 65536;  // rows of K_fu materialised at a time
 
 struct CompSpec {
   int nterms;
@@ -155,6 +156,8 @@ __device__ __forceinline__ double comp_grad(const CompSpec& cs, const double* a,
 // out[i][j] = k(a_i, b_j) (+ jitter on i == j) for i < na, j < nb, zero in the padding; rows_p x cols_p, ld cols_p
 void comp_kmatrix(const double* A, int64_t lda, int64_t na, const double* B, int64_t ldb, int nb, const CompSpec& cs, int d,
                   int64_t rows_p, int cols_p, double jitter, double* out, hipStream_t st);
+// bp[m] (+)= sum_{i < rows} K[i][m] y[i] for the Mp columns of K (ld ldk), in a fixed order
+void comp_colsum(const double* K, int64_t ldk, const double* y, int64_t rows, int Mp, int accumulate, double* bp, hipStream_t st);
 size_t comp_fwd_workspace_bytes(int64_t N, int M);
 int comp_suffstats_fwd(const double* X, int64_t ldx, const double* y, const double* Z, int64_t ldz, const CompSpec& cs,
                        int64_t N, int M, int d, double* Phi, double* b, double* yy, double* kappa, void* ws, size_t ws_bytes,
@@ -172,6 +175,12 @@ int comp_suffstats_bwd(const double* X, int64_t ldx, const double* y, const doub
 int comp_suffstats_bwd_factored(const double* X, int64_t ldx, const double* y, const double* Z, int64_t ldz, const CompSpec& cs,
                                 const double* Linv, const double* Cw, double s2, const double* bbar, double kappabar, int64_t N,
                                 int M, int d, double* g_blk, double* g_Z, void* ws, size_t ws_bytes, hipStream_t st);
+// g_blk[SGP_COMP_LEN] (OVERWRITTEN) = sum_nm Kfubar_nm dk(x_n, z_m)/d(.) with Kfubar = -2 T_in L^-1 + dmu w^T: the N-side gradient of
+// SGPMC with a composite kernel (include/sgp.h: sgp_sgpmc_comp_bwd).  T_in: round_up(N, 256) x Mp, Linv: Mp x Mp, w: M.
+size_t comp_sgpmc_bwd_workspace_bytes(int64_t N, int M);
+int comp_sgpmc_bwd(const double* X, int64_t ldx, const double* dmu, const double* Z, int64_t ldz, const CompSpec& cs, const double* T_in,
+                   const double* Linv, const double* w, int64_t N, int M, int d, double* g_blk, void* ws, size_t ws_bytes,
+                   hipStream_t st);
 size_t comp_kuu_bwd_workspace_bytes(int M, int d);
 // ADDS the Kuu contribution (Kuubar used as a symmetric matrix)
 int comp_kuu_bwd(const double* Z, int64_t ldz, const CompSpec& cs, const double* Kuubar, int M, int d, double* g_blk,

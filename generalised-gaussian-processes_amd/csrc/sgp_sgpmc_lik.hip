@@ -13,6 +13,7 @@
 #include "sgp_dense.hpp"
 #include "sgp_ctx.hpp"
 #include "sgp_lik.hpp"
+#include "sgp_sgpmc_lik.hpp"
 
 namespace sgp {
 
@@ -21,11 +22,16 @@ namespace sgp {
 // likelihood.  The per-workgroup partials [ell | ds2 | dv] are published with an agent-scope release and a ticket; the workgroup that
 // draws the last ticket adds them up in index order, so the sums do not depend on which workgroup that was.
 // LDS (dynamic, one array): v (Mp) | t.v of the rows (256) | |t|^2 of the rows (256) | block_sum256's 4 words | the "I am last" word.
+// The rows are a_n = scale T_n and k(x_n, x_n) = knn: (sf2, sf2) for the unit-amplitude T of a stationary kernel, (1, kdiag + white) for
+// the full-amplitude T of a composite one (sgp_sgpmc_comp.hip), which also brings the optional mean function `mean` (N, added to mu)
+// and the optional outputs mu_out / var_out (N; var as it is formed, not floored).  y == nullptr: the moments only -- no likelihood,
+// dmu = dv = 0 and zero sums (dmu / dv may be null then).
 __global__ __launch_bounds__(256) void sgpmc_lik_rows_kernel(const double* __restrict__ T, const double* __restrict__ y,
-                                                             const double* __restrict__ v, int64_t N, int M, int Mp, double sf2,
-                                                             double s2, int lik, GHTable gh, double* __restrict__ dmu,
-                                                             double* __restrict__ dv, double* __restrict__ dmu_pad,
-                                                             double* __restrict__ dv_pad, double* part,
+                                                             const double* __restrict__ mean, const double* __restrict__ v, int64_t N,
+                                                             int M, int Mp, double scale, double knn, double s2, int lik, GHTable gh,
+                                                             double* __restrict__ dmu, double* __restrict__ dv,
+                                                             double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                             double* __restrict__ dmu_pad, double* __restrict__ dv_pad, double* part,
                                                              int* __restrict__ counter, double* __restrict__ out) {
   extern __shared__ double lds[];
   double* vsh = lds;
@@ -63,14 +69,19 @@ __global__ __launch_bounds__(256) void sgpmc_lik_rows_kernel(const double* __res
   const int64_t n = rbase + tid;
   double ell = 0.0, gm = 0.0, gv = 0.0, gs = 0.0;
   if (n < N) {
-    const double mu = sf2 * tv[tid];
-    const double var = sf2 - (sf2 * sf2) * tt[tid];
-    lik_eval_floored(lik, y[n], mu, var, sf2 * 0x1p-40, s2, gh, ell, gm, gv, gs);
-    // dv <= 0 for these likelihoods, but a quadrature whose nodes are all saturated returns rounding noise of either sign around 0
-    // (1e-17 of dmu): a positive one is 0 here, so that sqrt(-dv) below is real.  (A NaN stays a NaN.)
-    if (gv > 0.0) gv = 0.0;
-    dmu[n] = gm;
-    dv[n] = gv;
+    double mu = scale * tv[tid];
+    if (mean) mu += mean[n];
+    const double var = knn - (scale * scale) * tt[tid];
+    if (mu_out) mu_out[n] = mu;
+    if (var_out) var_out[n] = var;
+    if (y) {
+      lik_eval_floored(lik, y[n], mu, var, knn * 0x1p-40, s2, gh, ell, gm, gv, gs);
+      // dv <= 0 for these likelihoods, but a quadrature whose nodes are all saturated returns rounding noise of either sign around 0
+      // (1e-17 of dmu): a positive one is 0 here, so that sqrt(-dv) below is real.  (A NaN stays a NaN.)
+      if (gv > 0.0) gv = 0.0;
+    }
+    if (dmu) dmu[n] = gm;
+    if (dv) dv[n] = gv;
   }
   dmu_pad[n] = gm;
   dv_pad[n] = gv;
@@ -144,6 +155,21 @@ __global__ __launch_bounds__(256) void sgpmc_lik_scale_kernel(double* __restrict
   }
 }
 
+void sgpmc_lik_rows_launch(const double* T, const double* y, const double* mean, const double* v, int64_t N, int64_t Npad, int M, int Mp,
+                           double scale, double knn, double s2, int lik, double* dmu, double* dv, double* mu_out, double* var_out,
+                           double* dmu_pad, double* dv_pad, double* part, int* counter, double* out, hipStream_t st) {
+  static const GHTable gh = make_gh();
+  const size_t lds = ((size_t)Mp + 2 * ASM_ROWS + 8) * sizeof(double);
+  sgpmc_lik_rows_kernel<<<(unsigned)(Npad / ASM_ROWS), 256, lds, st>>>(T, y, mean, v, N, M, Mp, scale, knn, s2, lik, gh, dmu, dv, mu_out,
+                                                                      var_out, dmu_pad, dv_pad, part, counter, out);
+}
+void sgpmc_lik_empty_launch(double* out, hipStream_t st) { sgpmc_lik_empty_kernel<<<1, 64, 0, st>>>(out); }
+void sgpmc_lik_scale_launch(double* T, const double* dv_pad, int64_t N, int64_t Npad, int M, int Mp, double sign, hipStream_t st) {
+  const int64_t groups = Npad / SCALE_ROWS;
+  const int sgrid = (int)(groups < SCALE_MAX_GROUPS ? groups : SCALE_MAX_GROUPS);
+  sgpmc_lik_scale_kernel<<<sgrid, 256, 0, st>>>(T, dv_pad, N, Npad, M, Mp, sign);
+}
+
 struct LikRowsWs {
   WhRowsWs wh;
   double *dmu_pad, *dv_pad, *part, *scratch;
@@ -199,7 +225,7 @@ extern "C" int sgp_sgpmc_lik_rows(const double* X, int64_t ldx, const double* y,
   hipStream_t st = (hipStream_t)stream;
   const FwdWs& f = w.wh.f;
   if (p.Npad == 0) {
-    sgpmc_lik_empty_kernel<<<1, 64, 0, st>>>(out);
+    sgpmc_lik_empty_launch(out, st);
     if (want_adjoints) {
       fill_zero(G, (size_t)M * M, st);
       fill_zero(g, (size_t)M, st);
@@ -214,19 +240,15 @@ extern "C" int sgp_sgpmc_lik_rows(const double* X, int64_t ldx, const double* y,
   t.A = f.Kfu; t.lda = p.Mp; t.B = w.wh.R; t.ldb = p.Mp; t.C = T_out; t.ldc = p.Mp;
   t.m = (int)p.Npad; t.n = p.Mp; t.k = p.Mp; t.khi_mask = 2;
   gemm(t, st);
-  static const GHTable gh = make_gh();
-  const size_t lds = ((size_t)p.Mp + 2 * ASM_ROWS + 8) * sizeof(double);
-  sgpmc_lik_rows_kernel<<<(unsigned)(p.Npad / ASM_ROWS), 256, lds, st>>>(T_out, y, v, N, M, p.Mp, sf2, s2, likelihood_id, gh, dmu, dv,
-                                                                        w.dmu_pad, w.dv_pad, w.part, w.counter, out);
+  sgpmc_lik_rows_launch(T_out, y, nullptr, v, N, p.Npad, M, p.Mp, sf2, sf2, s2, likelihood_id, dmu, dv, nullptr, nullptr, w.dmu_pad,
+                        w.dv_pad, w.part, w.counter, out, st);
   if (!want_adjoints) return check_launch();
   // g = sf2 T^T dmu: the partials and the reduction of K'^T y (yy and kappa of that reduction go to scratch)
   launch_tpart(T_out, w.dmu_pad, 0, p.Npad, p.Mp, f.bpart, st);
   reduce_bparts(p, f.bpart, f.btmp, f.yypart, 1, sf2, N, M, g, w.scratch, w.scratch + 1, st);
-  const int64_t groups = p.Npad / SCALE_ROWS;
-  const int sgrid = (int)(groups < SCALE_MAX_GROUPS ? groups : SCALE_MAX_GROUPS);
-  sgpmc_lik_scale_kernel<<<sgrid, 256, 0, st>>>(T_out, w.dv_pad, N, p.Npad, M, p.Mp, 1.0);
+  sgpmc_lik_scale_launch(T_out, w.dv_pad, N, p.Npad, M, p.Mp, 1.0, st);
   launch_syrk(cx, T_out, p.Mp, p.Npad / NB, split_map(p.taper, p.Npad / NB, p.nsplit), p.ntiles, p.nsplit, 0, f.slab, st);
   reduce_slabs(p, f.slab, p.nsplit, M, -(sf2 * sf2), G, st);
-  sgpmc_lik_scale_kernel<<<sgrid, 256, 0, st>>>(T_out, w.dv_pad, N, p.Npad, M, p.Mp, -1.0);
+  sgpmc_lik_scale_launch(T_out, w.dv_pad, N, p.Npad, M, p.Mp, -1.0, st);
   return check_launch();
 }

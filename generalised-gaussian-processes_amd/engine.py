@@ -538,6 +538,70 @@ class HipEngine:
         _lib.check("sgp_sgpmc_lik_tail", st)
         return res
 
+    def sgpmc_comp_rows(self, X, y, Z, block, white, s2, v, kuu_linv, t_out, likelihood="gaussian", mean=None, want_adjoints=False,
+                        want_moments=False):
+        """The SGPMC row pass for a composite kernel with a white-noise term and a mean function (include/sgp.h: sgp_sgpmc_comp_rows).
+        ``block``: the kernel's parameter block (host list); ``white`` >= 0; ``mean`` (N doubles on the device, or None): m(x_n);
+        ``kuu_linv`` from ``kuu_factor(kuu(Z, block, 1.0, jitter + white, "composite"))``.  ``y = None``: the conditional moments only
+        (prediction).  ``t_out`` (from ``kfu_buffer``) holds T = K_fu L^-T on return, diag(dv) T with the adjoints -- what
+        ``sgpmc_comp_bwd`` takes.
+
+        Returns dict(out = [sum ell | d sum ell / d s2 | sum dv], dmu, dv (N), with the adjoints g (M), G (M x M), with ``want_moments``
+        (or ``y = None``) mu, var (N)).  Nothing is synchronised."""
+        N, d = X.shape
+        M = Z.shape[0]
+        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv"), self._chk(v, "v"), self._chk(t_out, "t_out")
+        if N > 0:
+            self._chk(X, "X")
+            for t, name in ((y, "y"), (mean, "mean")):
+                if t is not None and (self._chk(t, name).numel() != N):
+                    raise ValueError("%s has %d entries, X has %d rows" % (name, t.numel(), N))
+        if v.numel() != M:
+            raise ValueError("v has %d entries, Z has %d rows" % (v.numel(), M))
+        if t_out.numel() < self.lib.sgp_kfu_len(N, M):
+            raise ValueError("t_out holds %d doubles, sgp_kfu_len(N, M) = %d" % (t_out.numel(), self.lib.sgp_kfu_len(N, M)))
+        if y is None and want_adjoints:
+            raise ValueError("sgpmc_comp_rows(y=None) returns the moments only: there are no adjoints")
+        nbytes = self._cf.sgp_sgpmc_comp_rows_workspace_bytes(N, M, d)
+        if nbytes == 0:
+            raise ValueError("unsupported shape N=%d M=%d d=%d (a composite kernel takes d <= 8)" % (N, M, d))
+        ws = self._workspace("sgpmc_comp_rows", nbytes)
+        res = {"out": self.empty(_lib.SGPMC_LIK_OUT_LEN), "dmu": self.empty(N), "dv": self.empty(N)}
+        if want_adjoints:
+            res.update(g=self.empty(M), G=self.empty(M, M))
+        if want_moments or y is None:
+            res.update(mu=self.empty(N), var=self.empty(N))
+        st = self._cf.sgp_sgpmc_comp_rows(
+            self._ptr(X), d, self._ptr(y), self._ptr(mean), self._ptr(Z), d, self._inv_ls(block, d, "composite"), float(white), float(s2),
+            self._ptr(v), N, M, d, _likelihood_id(likelihood), self._ptr(kuu_linv), 1 if want_adjoints else 0, self._ptr(res["out"]),
+            self._ptr(res.get("G")), self._ptr(res.get("g")), self._ptr(res["dmu"]), self._ptr(res["dv"]), self._ptr(res.get("mu")),
+            self._ptr(res.get("var")), self._ptr(t_out), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_comp_rows", st)
+        return res
+
+    def sgpmc_comp_bwd(self, X, dmu, Z, block, t_in, kuu_linv, bbar, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The N-side gradient behind ``sgpmc_comp_rows`` (include/sgp.h: sgp_sgpmc_comp_bwd): ``out[:COMP_LEN]`` is overwritten with
+        sum_nm Kfubar_nm dk(x_n, z_m)/d block, Kfubar = -2 t_in L^-1 + dmu bbar^T (``t_in``: ``t_out`` after a call with the adjoints,
+        ``bbar`` = L^-T v from ``sgpmc_lik_tail``).  ``out`` holds COMP_LEN + 1 doubles, the layout ``kuu_bwd(kernel="composite")`` adds
+        the K_uu side into.  Nothing is synchronised."""
+        N, d = X.shape
+        M = Z.shape[0]
+        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv"), self._chk(t_in, "t_in"), self._chk(bbar, "bbar")
+        if N > 0:
+            self._chk(X, "X"), self._chk(dmu, "dmu")
+        if out is None:
+            out = self.empty(COMP_LEN + 1)
+            out[COMP_LEN:].zero_()
+        nbytes = self._cf.sgp_sgpmc_comp_bwd_workspace_bytes(N, M, d)
+        if nbytes == 0:
+            raise ValueError("unsupported shape N=%d M=%d d=%d (a composite kernel takes d <= 8)" % (N, M, d))
+        ws = self._workspace("sgpmc_comp_bwd", nbytes)
+        st = self._cf.sgp_sgpmc_comp_bwd(self._ptr(X), d, self._ptr(dmu), self._ptr(Z), d, self._inv_ls(block, d, "composite"),
+                                         self._ptr(t_in), self._ptr(kuu_linv), self._ptr(bbar), N, M, d, C.c_void_p(out.data_ptr()),
+                                         self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_comp_bwd", st)
+        return out
+
     # ------------------------------------------------------------------ single-launch path for small problems
     def small_supported(self, N: int, M: int, d: int, kernel="rbf") -> bool:
         return bool(self._cf.sgp_small_supported(int(N), int(M), int(d), _kernel_id(kernel)))

@@ -17,6 +17,7 @@ import time
 import numpy as np
 import torch
 
+from .composite import CompositeSgpmcTarget
 from .hmc import sample_hmc
 from .targets import SgpmcTarget
 
@@ -26,6 +27,23 @@ class SgpmcModel:
     (``Z``, frozen during sampling) and the warm-up's record."""
 
     def __init__(self, target: SgpmcTarget):
+        self.target = target
+        self.engine = target.engine
+        self.kernel = target.kernel
+        self.jitter = target.jitter
+        self.likelihood = target.likelihood
+        self.warmup = {}
+
+    @property
+    def Z(self):
+        return self.target.Z
+
+
+class CompositeSgpmcModel:
+    """What ``train_sgp_hmc_composite`` returns as ``model``: the ``CompositeSgpmcTarget`` (data, kernel structure, white / mean
+    switches, jitter, engine) and the frozen inducing inputs."""
+
+    def __init__(self, target: CompositeSgpmcTarget):
         self.target = target
         self.engine = target.engine
         self.kernel = target.kernel
@@ -87,6 +105,28 @@ def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed
     return model, trace, wall_clock_secs
 
 
+def train_sgp_hmc_composite(data, Z_init, kernel, tune, num_samples, priors=None, mean="linear", white=1.0, likelihood="gaussian",
+                            engine=None, seed=None, num_leapfrog_steps=20, step_size=0.005, num_adaptation_steps=20, target_accept=0.8,
+                            adaptation_rate=0.05):
+    """experiments/co2_sgpmc.py:57-144: SGPMC with a sum-of-products ``kernel`` (``composite.CompositeKernel``), a White term
+    (``white``: its start value, None for none), a linear mean function and per-parameter ``priors``
+    (``composite.CompositeSgpmcTarget``); returns ``(model, trace, wall_clock_secs)``.  As the reference: jitter 1e-4 (:22), no warm-up
+    (commented out, :105-107), Z frozen (:108), ``sample_hmc`` from the start values with 20 leapfrog steps, step 0.005, 20 adaptation
+    steps, target 0.8, rate 0.05 (:120-126).  ``wall_clock_secs`` times the sampling only."""
+    X, Y = _as_tensor(data[0]), _as_tensor(data[1]).reshape(-1)
+    if X.dim() == 1:
+        X = X[:, None]
+    target = CompositeSgpmcTarget(X, Y, _as_tensor(Z_init), kernel, priors=priors, white=white, mean=mean, likelihood=likelihood,
+                                  jitter=1e-4, engine=engine)
+    model = CompositeSgpmcModel(target)
+    t0 = time.time()
+    trace = sample_hmc(target, int(num_samples), int(tune), seed=seed, start=target.start(), num_leapfrog_steps=num_leapfrog_steps,
+                       step_size=step_size, num_adaptation_steps=num_adaptation_steps, target_accept=target_accept,
+                       adaptation_rate=adaptation_rate)
+    wall_clock_secs = time.time() - t0
+    return model, trace, wall_clock_secs
+
+
 def likelihood_moments(likelihood, mu, var):
     """(E y, sd y) of y | f ~ likelihood with f ~ N(mu, var), elementwise:
     Bernoulli (y in {0, 1}): p and sqrt(p (1 - p)) with p = Phi(mu / sqrt(1 + var)) for the probit link, the 20-point Gauss-Hermite
@@ -112,7 +152,12 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
     the FIRST 50 draws of the chain; ``n_draws`` keeps that default (fewer when the trace is shorter).  Per draw ``predict_f`` is the
     whitened SVGP predictive with q(v) a point mass, ``engine.svgp_predict(m=v, LS=0)``: mean = a^T v, var = k** - |a|^2 with
     a = L^-1 k_u*; y_std = sqrt(var + noise variance).  With a non-Gaussian likelihood ``f_means`` and ``y_stds`` hold the likelihood's
-    conditional moments of y per draw (``likelihood_moments``) and ``pred_mean`` their mean over the draws."""
+    conditional moments of y per draw (``likelihood_moments``) and ``pred_mean`` their mean over the draws.
+
+    A ``CompositeSgpmcModel`` (``train_sgp_hmc_composite``) is predicted by ``sgpmc_comp_rows`` on X_test without labels, per draw:
+    mean = a^T v + m(x*), var = kdiag + white - |a|^2."""
+    if isinstance(model, CompositeSgpmcModel):
+        return _predict_composite(model, trace, X_test, n_draws)
     e = model.engine
     Xs = _as_tensor(X_test)
     if Xs.dim() == 1:
@@ -134,6 +179,39 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
         if model.likelihood == "gaussian":
             f_means.append(mean)
             y_stds.append(np.sqrt(var + float(row["noise_variance"])))
+        else:
+            ym, ys = likelihood_moments(model.likelihood, mean, var)
+            f_means.append(ym)
+            y_stds.append(ys)
+    f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
+    return np.mean(f_means, axis=0), f_means, y_stds
+
+
+def _predict_composite(model, trace, X_test, n_draws):
+    e, t = model.engine, model.target
+    Xs = _as_tensor(X_test)
+    if Xs.dim() == 1:
+        Xs = Xs[:, None]
+    Xs = Xs.to(e.device).contiguous()
+    Z, M, T = model.Z, int(model.Z.shape[0]), int(Xs.shape[0])
+    n = min(int(n_draws), len(trace))
+    if n <= 0:
+        raise ValueError("the trace holds no draws")
+    t_buf = e.kfu_buffer(T, M)
+    f_means, y_stds = [], []
+    for i in range(n):
+        q = trace[i]["theta_unc"]
+        block, white, s2, A, b, _ = t.unpack(q)
+        linv, info = e.kuu_factor(e.kuu(Z, block, 1.0, model.jitter + white, "composite"))
+        v = torch.as_tensor(np.asarray(q[t.n_theta:], dtype=np.float64)).to(e.device).contiguous()
+        m = None if A is None else (Xs @ torch.tensor(A, dtype=torch.float64).to(e.device) + b).contiguous()
+        r = e.sgpmc_comp_rows(Xs, None, Z, block, white, 1.0, v, linv, t_buf, model.likelihood, mean=m)
+        mean, var = r["mu"].detach().to("cpu").numpy(), np.maximum(r["var"].detach().to("cpu").numpy(), 0.0)
+        if int(info.item()) != 0:
+            raise RuntimeError("K_uu of draw %d is not positive definite (status %d)" % (i, int(info.item())))
+        if model.likelihood == "gaussian":
+            f_means.append(mean)
+            y_stds.append(np.sqrt(var + s2))
         else:
             ym, ys = likelihood_moments(model.likelihood, mean, var)
             f_means.append(ym)

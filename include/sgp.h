@@ -546,6 +546,43 @@ int sgp_sgpmc_lik_tail(const double* rows_out, const double* G, const double* g,
                        double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
                        sgp_stream_t stream);
 
+/* ---- SGPMC with a composite kernel, a white-noise term and a mean function ----------------------------------------------------------
+ * The model of the reference's experiments/co2_sgpmc.py: a sum-of-products covariance (`block`, HOST, SGP_COMP_LEN doubles) plus
+ * white noise of variance `white` >= 0, and a mean function m(x).  [UPSTREAM] GPflow's White.K(Z, X) is 0 for two different sets of
+ * inputs, as recalled: white enters K_uu's diagonal and k(x, x) only -- the caller passes sgp_kuu the jitter J + white, and `white`
+ * here.  A composite kernel has no unit-amplitude split, so T = K_fu L^-T carries the full amplitude and its rows are a_n^T:
+ *   K = k(Z, Z) + (J + white) I = L L^T     a_n = L^-1 k(Z, x_n)     k_nn = (sum of the block's amp2 slots) + white
+ *   mu_n = a_n.v + m_n     var_n = k_nn - |a_n|^2  (below 2^-40 k_nn: raised to it, dv_n = 0)     ell_n = E_{N(mu_n, var_n)} log p(y_n | f)
+ *   F(v, theta) = sum_n ell_n - 1/2 v.v - M/2 log(2 pi)       g = sum_n dmu_n a_n     G = sum_n dv_n a_n a_n^T  ->  sgp_sgpmc_lik_tail
+ *   Kfubar row n = dmu_n w^T - 2 dv_n a_n^T L^-1              (w = bbar = L^-T v of the tail)
+ *   dF/dtheta_k = sum_nm Kfubar_nm dk(x_n, z_m)/dtheta_k + sum_ij Kuubar_ij dk(z_i, z_j)/dtheta_k + (sum_n dv_n) [theta_k is an amp2 slot]
+ *   dF/dwhite = tr(Kuubar) + sum_n dv_n     dF/dm_n = dmu_n     dF/ds2 = sum_n ds2_n (Gaussian)     dF/dv = vbar
+ * sgp_sgpmc_comp_rows: K_fu materialised COMP_CHUNK_ROWS (65536) rows at a time, T = K_fu L^-T into T_out (DEVICE, sgp_kfu_len(N, M)
+ * doubles, required, the whole shard), then the row pass of sgp_sgpmc_lik_rows.  X (N x d, d <= 8), Z, v, kuu_linv as there.
+ *   y (DEVICE, N, or NULL)      NULL: the moments only (prediction) -- no likelihood, out = 0, dmu / dv may be NULL, no adjoints
+ *   mean (DEVICE, N, or NULL)   m(x_n), added to mu_n
+ *   out (DEVICE, SGP_SGPMC_LIK_OUT_LEN) = [sum ell | sum ds2 | sum dv]: what sgp_sgpmc_lik_tail reads;  dmu, dv (DEVICE, N)
+ *   mu, var (DEVICE, N, each may be NULL)   the conditional moments, var as formed (not floored)
+ *   want_adjoints != 0: g (M), G (M x M, ld M) and T_out = diag(dv) T with zero padding; 0: T_out = T, G and g may be NULL.
+ * Every sum runs in a fixed order: the same inputs give the same bits, whatever the workspace and T_out held before.  Non-finite
+ * intermediates reach `out` as values, never an address.  N = 0 is legal.
+ * sgp_sgpmc_comp_bwd: g_blk (DEVICE, SGP_COMP_LEN, OVERWRITTEN) = sum_nm Kfubar_nm dk(x_n, z_m)/d block from T_in (what T_out holds after
+ * a call with adjoints), dmu, kuu_linv and bbar = w: one product -2 T_in L^-1 per row chunk and the composite path's gradient
+ * contraction.  sgp_kuu_bwd follows unchanged and ADDS the K_uu side; the amp2 term sum dv and dF/dwhite are the caller's (host scalars
+ * after its one copy).  There is no dF/dZ.
+ * SGP_ERR_ARG: a NULL required pointer, ldx / ldz < d, a block the composite path rejects, d > 8, likelihood id out of range, Gaussian
+ * with s2 <= 0, white < 0, adjoints without G / g / y; SGP_ERR_DIM: M > SGP_MAX_INDUCING; SGP_ERR_WORKSPACE: NULL or short workspace.
+ * All of them before any launch.                                                                                                    */
+size_t sgp_sgpmc_comp_rows_workspace_bytes(int64_t N, int M, int d);
+int sgp_sgpmc_comp_rows(const double* X, int64_t ldx, const double* y, const double* mean, const double* Z, int64_t ldz,
+                        const double* block, double white, double s2, const double* v, int64_t N, int M, int d, int likelihood_id,
+                        const double* kuu_linv, int want_adjoints, double* out, double* G, double* g, double* dmu, double* dv,
+                        double* mu, double* var, double* T_out, void* ws, size_t ws_bytes, sgp_stream_t stream);
+size_t sgp_sgpmc_comp_bwd_workspace_bytes(int64_t N, int M, int d);
+int sgp_sgpmc_comp_bwd(const double* X, int64_t ldx, const double* dmu, const double* Z, int64_t ldz, const double* block,
+                       const double* T_in, const double* kuu_linv, const double* bbar, int64_t N, int M, int d, double* g_blk,
+                       void* ws, size_t ws_bytes, sgp_stream_t stream);
+
 /* ---- single-launch evaluation for small problems (M <= 128; stationary kernels d <= 24, composite d <= 8) -------------------------
  * The size class of the reference's own HMC runs (models/bayesian_sgpr_hmc.py:58-80,144-157: N ~ 250-1300, M = 100).
  * ONE cooperative kernel launch evaluates the bound and its gradient in the PyMC3 op order (A = L^-1 K_uf by blocked
