@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""The reference's hyper-parameter identification study (experiments/hyperparameter_identification.py and experiments/lml_surface.py)
+on the batched exact-GP entry point: where ML-II fails, and why one samples theta instead.
+
+  * data: draws of a GP prior (sig_f = 5, lengthscale 2) on a 500-point grid of [0, 10], observed with noise at n grid points chosen
+    uniformly (or, ``--bimodal``, around 2 and 8) -- ``ggp_amd.identification_data``;
+  * size sweep: ML-II (``ggp_amd.fit_ml2``: theta0 = 1, 10 restarts, lengthscale in [1e-2, 1e3]) on ``--n_sets`` data sets at each of
+    ``--sizes`` training sizes, noise fixed at its true value and learnt;
+  * noise sweep: the same at n = 30 for noise variances 1, 3, 6, 9 (5 restarts, lengthscale in [1e-2, 1e4]), fixed and learnt;
+  * three LML surfaces (``ggp_amd.lml_surface``): (sf2, ls) at n = 5 and n = 10 with the noise at 1, and (ls, s2) at n = 30 with sf2 at
+    its fitted value -- one launch each.
+
+Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
+figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ggp_amd  # noqa: E402
+
+TRUE = {"sig_sd": 5.0, "lengthscale": 2.0, "noise_sd": 1.0}
+AMP_BOUNDS = (1e-5, 1e5)
+
+
+def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed):
+    """cells: [(label, n_train, noise variance)].  Fits every cell with the noise fixed at its true variance and with the noise learnt.
+    Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data."""
+    res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
+    data = []
+    for _, n, var in cells:
+        X, Y, latent = ggp_amd.identification_data(n, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
+            k: TRUE[k] for k in ("sig_sd", "lengthscale")})
+        data.append((X, Y))
+        bounds = np.array([(1e-2, ls_upper), AMP_BOUNDS, AMP_BOUNDS])
+        for mode in ("fixed", "learn"):
+            fit = ggp_amd.fit_ml2(X, Y, noise=mode, theta0=[1.0, 1.0, float(var)], bounds=bounds, n_restarts=n_restarts, seed=seed,
+                                  engine=engine)
+            r = res[mode]
+            r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
+            r["lml"].append(fit.lml), r["n_batches"].append(fit.n_batches)
+    return {m: {k: np.array(v) for k, v in r.items()} for m, r in res.items()}, data, latent
+
+
+def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n_sets=100, grid=50, n_noise=30, bimodal=False, seed=57,
+        engine=None):
+    rng = np.random.default_rng(seed)
+    out, summary = {}, {"sizes": list(sizes), "noise_vars": list(noise_vars), "n_sets": n_sets, "true": TRUE}
+    t0 = time.time()
+    size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed)
+    noise_res, noise_data, latent = sweep([(v, n_noise, float(v)) for v in noise_vars], n_sets, 1e4, 5, rng, latent, not bimodal, engine,
+                                          seed)
+    summary["fit_seconds"] = time.time() - t0
+    for name, res in (("size", size_res), ("noise", noise_res)):
+        for mode, r in res.items():
+            for k, v in r.items():
+                out["%s_%s_%s" % (name, mode, k)] = v
+            summary["%s_%s_mean_log_ls" % (name, mode)] = np.log(r["ls"].mean(1)).tolist()
+            summary["%s_%s_batched_evaluations" % (name, mode)] = r["n_batches"].tolist()
+    # surfaces: (sf2, ls) at the two smallest sizes available, noise at 1; (ls, s2) on the first noise cell with sf2 at its fit
+    t0 = time.time()
+    ax = np.logspace(-1, 4, grid)
+    for tag, n in (("n5", 5), ("n10", 10)):
+        X, Y, latent = ggp_amd.identification_data(n, 1, rng, latent=latent, **TRUE)
+        out["surface_%s_X" % tag], out["surface_%s_y" % tag] = X, Y[0]
+        out["surface_%s" % tag] = ggp_amd.lml_surface(X, Y[0], ax[:, None], ax[None, :], 1.0, engine=engine)  # [sf2, ls]
+    Xn, Yn = noise_data[0]
+    k = min(7, n_sets - 1)
+    sf2_fit = float(noise_res["learn"]["sf"][0][k] ** 2)
+    ax5 = np.logspace(-1, 5, grid)
+    out["surface_noise"] = ggp_amd.lml_surface(Xn, Yn[k], sf2_fit, ax5[:, None], ax5[None, :], engine=engine)        # [ls, s2]
+    out["surface_axis"], out["surface_noise_axis"] = ax, ax5
+    summary["surface_seconds"] = time.time() - t0
+    summary["surface_cells"] = int(3 * grid * grid)
+    summary["surface_nan_cells"] = int(sum(np.isnan(out[k]).sum() for k in ("surface_n5", "surface_n10", "surface_noise")))
+    return out, summary
+
+
+def plot(out, summary, path):
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return False
+    fig, axs = plt.subplots(1, 3, figsize=(13, 3.6))
+    for mode, c in (("fixed", "b"), ("learn", "g")):
+        axs[0].plot(summary["sizes"], summary["size_%s_mean_log_ls" % mode], c + "o-", label="noise " + mode)
+        axs[1].plot(summary["noise_vars"], summary["noise_%s_mean_log_ls" % mode], c + "o-", label="noise " + mode)
+    for a, lab in ((axs[0], "training set size"), (axs[1], "noise variance")):
+        a.axhline(np.log(TRUE["lengthscale"]), color="r")
+        a.set_xlabel(lab), a.set_ylabel("log of the mean fitted lengthscale"), a.legend(fontsize="small")
+    neg = -out["surface_n10"]
+    axs[2].contourf(out["surface_axis"], out["surface_axis"], np.minimum(neg, 100.0).T, levels=40)
+    axs[2].set_xscale("log"), axs[2].set_yscale("log"), axs[2].set_xlabel("signal variance"), axs[2].set_ylabel("lengthscale")
+    axs[2].set_title("negative LML, n = 10", fontsize="small")
+    fig.tight_layout()
+    fig.savefig(path, dpi=120)
+    return True
+
+
+def main(argv=None, engine=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[10, 15, 20, 25, 40, 60, 80, 100, 120])
+    ap.add_argument("--noise_vars", type=float, nargs="+", default=[1, 3, 6, 9])
+    ap.add_argument("--n_sets", type=int, default=100)
+    ap.add_argument("--grid", type=int, default=50)
+    ap.add_argument("--bimodal", action="store_true", help="inputs around 2 and 8 instead of uniform on the grid")
+    ap.add_argument("--seed", type=int, default=57)
+    ap.add_argument("--out", default="results")
+    args = ap.parse_args(argv)
+    out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine)
+    os.makedirs(args.out, exist_ok=True)
+    base = os.path.join(args.out, "hyperparameter_identification")
+    np.savez_compressed(base + ".npz", **out)
+    summary["figure"] = plot(out, summary, base + ".png")
+    with open(base + ".json", "w") as fh:
+        json.dump(summary, fh, indent=1)
+    print(json.dumps(summary))
+    return summary
+
+
+if __name__ == "__main__":
+    main()

@@ -12,6 +12,7 @@ from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianL
                       MultivariateNormal, PoissonLikelihood, RBFKernel, ScaleKernel, ZeroMean, settings)
 from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_device  # noqa: F401
 from .metrics import negative_log_predictive_mixture_density, nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
+from .ml2 import Ml2Result, fit_ml2, identification_data, lml_surface  # noqa: F401
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
 from .sgp_hmc import (CompositeSgpmcModel, SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments,  # noqa: F401

@@ -214,6 +214,12 @@ PROTOTYPES = {
     "sgp_exact_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_ctx_exact_predict": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dbl, _dbl, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                      _sz, _vp]),
+    # P exact marginal likelihoods in one launch (LML surfaces, multi-start ML-II)
+    "sgp_exact_batch_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "sgp_exact_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_exact_eval_batch": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_ctx_exact_eval_batch": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                        _sz, _vp]),
     "sgp_predict_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "sgp_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _i32, _i32, _i32, _i32,
                            _vp, _vp, _vp, _vp, _sz, _vp]),

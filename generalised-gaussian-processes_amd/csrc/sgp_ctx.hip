@@ -283,3 +283,12 @@ extern "C" int sgp_ctx_exact_predict(sgp_ctx* ctx, const double* Xs, int64_t ldx
   return sgp_exact_predict(Xs, ldxs, T, X, ldx, N, d, inv_ls, sf2, s2, factors, kernel_id, pred_noise, mean, var, cov, ws, ws_bytes,
                            stream);
 }
+extern "C" int sgp_ctx_exact_eval_batch(sgp_ctx* ctx, const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride,
+                                        const int* ix, const int* iy, const double* theta, int64_t P, int N, int d, int kernel_id,
+                                        int with_grad, double* out, double* grads, int* info, void* ws, size_t ws_bytes,
+                                        sgp_stream_t stream) {
+  if (!ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  CtxScope scope(ctx);
+  return sgp_exact_eval_batch(X, x_stride, ldx, Y, y_stride, ix, iy, theta, P, N, d, kernel_id, with_grad, out, grads, info, ws, ws_bytes,
+                              stream);
+}

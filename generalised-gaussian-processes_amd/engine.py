@@ -896,6 +896,45 @@ class HipEngine:
             res["factors"] = factors
         return res
 
+    def _set_index(self, idx, n_sets: int, P: int, name: str):
+        """ix / iy of ``exact_eval_batch`` as a device int32 tensor of P entries, or None.  A host sequence is range-checked here (it
+        costs nothing); a device tensor is taken as it is -- the caller answers for its range, nothing is copied to the host."""
+        if idx is None:
+            return None
+        if isinstance(idx, torch.Tensor) and idx.device == self.device:
+            if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != P:
+                raise ValueError("%s must be a contiguous int32 tensor of %d entries" % (name, P))
+            return idx
+        host = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx).reshape(-1)
+        if host.size != P or (P and (host.min() < 0 or host.max() >= n_sets)):
+            raise ValueError("%s must hold %d indices in [0, %d)" % (name, P, n_sets))
+        return torch.as_tensor(host.astype(np.int32), device=self.device)
+
+    def exact_eval_batch(self, X, Y, theta, ix=None, iy=None, kernel="rbf", want_grad=True):
+        """P exact marginal likelihoods in ONE launch (include/sgp.h: sgp_exact_eval_batch).  X: nX x N x d (or N x d), Y: nY x N (or
+        N), theta: P x (d + 2) rows [ls_1..d | sf2 | s2] -- device tensors; problem p takes data set ix[p] and target iy[p] (None: set
+        0).  Returns device tensors (F [P], out [P, 4], grads [P, d + 2] or None, info [P] int32); nothing is synchronised and nothing
+        is copied to the host.  A problem with info != 0 has NaN rows."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        nX, N, d = X.shape
+        nY = Y.shape[0]
+        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(theta, "theta")
+        if Y.shape[1] != N or theta.dim() != 2 or theta.shape[1] != d + 2:
+            raise ValueError("shapes: X %s, Y %s, theta %s (expected theta P x %d)" % (tuple(X.shape), tuple(Y.shape), tuple(theta.shape), d + 2))
+        P = theta.shape[0]
+        ix, iy = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy")
+        out = self.empty(P, 4)
+        grads = self.empty(P, d + 2) if want_grad else None
+        info = torch.empty(P, dtype=torch.int32, device=self.device)
+        ws = self._workspace("exact_batch", self.lib.sgp_exact_batch_workspace_bytes(P, N, d, 1 if want_grad else 0))
+        st = self.lib.sgp_ctx_exact_eval_batch(
+            self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), self._ptr(theta), P, N, d,
+            _kernel_id(kernel), 1 if want_grad else 0, self._ptr(out), self._ptr(grads), self._ptr(info), self._ptr(ws), ws.numel(),
+            self._stream())
+        _lib.check("sgp_exact_eval_batch", st)
+        return out[:, 0], out, grads, info
+
     def exact_predict(self, Xs, X, ls, sf2, s2, factors, kernel="rbf", pred_noise=True, full_cov=False):
         """Exact posterior predictive at the rows of Xs from ``exact_eval(..., want_factors=True)``'s factors at the same (X, theta)
         (include/sgp.h: sgp_exact_predict).  Returns (mean, var, cov or None) as device tensors; nothing is synchronised."""

@@ -862,6 +862,34 @@ int sgp_exact_predict(const double* Xs, int64_t ldxs, int64_t T, const double* X
 int sgp_ctx_exact_predict(sgp_ctx* ctx, const double* Xs, int64_t ldxs, int64_t T, const double* X, int64_t ldx, int64_t N, int d,
                           const double* inv_ls, double sf2, double s2, const double* factors, int kernel_id, int pred_noise, double* mean,
                           double* var, double* cov, void* ws, size_t ws_bytes, sgp_stream_t stream);
+/* ---- P independent exact-GP marginal likelihoods in ONE launch (LML surfaces, multi-start ML-II; csrc/sgp_exact_batch.hip) ----
+ * Problem p is F = log N(Y[iy[p]] | 0, sf2 k'(X[ix[p]], X[ix[p]]) + s2 I) at the row theta[p] = [ls_1..ls_d | sf2 | s2]; one
+ * workgroup per problem, the whole problem in its LDS, no communication between problems.
+ *   1 <= N <= 128, 1 <= d <= 8, 1 <= P < 2^24 (P x 256 work-items stay below the 2^32 of one launch), kernel_id 0..2
+ *   (SGP_KERNEL_COMPOSITE -> SGP_ERR_ARG); anything else is refused before anything is enqueued (SGP_ERR_ARG / SGP_ERR_DIM /
+ *   SGP_ERR_WORKSPACE).  ALL arrays are DEVICE arrays:
+ *   X (data set s: N rows of leading dimension ldx >= d at X + s x_stride), Y (target s: N doubles at Y + s y_stride),
+ *   ix, iy (P ints each, or NULL = every problem uses set 0; the caller answers for their range), theta (P x (d + 2))
+ *   out (P x 4) = [F, y^T A^-1 y, log|A|, tr A^-1 (NaN when with_grad == 0)]
+ *   grads (P x (d + 2), with_grad != 0) = [dF/dls_1..d | dF/dsf2 | dF/ds2], sgp_exact_eval's convention
+ *   info (P ints): 0, or k > 0: the first pivot that is not above 8 N 2^-53 (sf2 + s2) -- A is not numerically positive
+ *     definite at row k.  A row of theta with an entry that is not a positive finite number (NaN, 0, negative, infinite) is
+ *     tested for that and reports k = 1.  That problem's out and grads rows are NaN; its neighbours are untouched; it is never an
+ *     error return.
+ * Accuracy: substitution against the Cholesky factor for the value, the explicit L^-1 for the gradient.  Against a long-double
+ * evaluation  |F - ref| <= 1e-12 S_F  and  |g - ref| <= 1e-12 cond_2(A) S_g  component-wise, with the condition scales
+ *   S_F = (|alpha|^T |A| |alpha| + sum |A^-1| o |A|) / 2 ,  S_g[theta] = sum (|alpha| |alpha|^T + |A^-1|) o |dA/dtheta| / 2
+ * (tests/exact_batch_reference.py).  Every sum runs in a fixed order inside the problem: the same bits on every call, on every
+ * stream and whatever else shares the launch; the value is the same bits with and without the gradient.  A^-1 is never stored. */
+size_t sgp_exact_batch_workspace_bytes(int64_t P, int N, int d, int with_grad);
+/* workgroups (= problems) of N's size class resident on one CU, from the runtime's occupancy query; < 0: a status (no launch) */
+int sgp_exact_batch_occupancy(int N, int kernel_id);
+int sgp_exact_eval_batch(const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride, const int* ix,
+                         const int* iy, const double* theta, int64_t P, int N, int d, int kernel_id, int with_grad, double* out,
+                         double* grads, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+int sgp_ctx_exact_eval_batch(sgp_ctx* ctx, const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride,
+                             const int* ix, const int* iy, const double* theta, int64_t P, int N, int d, int kernel_id, int with_grad,
+                             double* out, double* grads, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
 
 /* host utility: n-point Gauss-Hermite rule for the standard normal (sum w_i f(x_i) ~ E f(N(0,1))) */
 int sgp_gauss_hermite(int n, double* x, double* w);
