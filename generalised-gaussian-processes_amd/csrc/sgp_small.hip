@@ -864,10 +864,40 @@ __device__ __forceinline__ void sm_eval_body(const SmallArgs& a, SmKernelShared<
     const double logmarg = -(0.5 * Nd * LOG2PI + 0.5 * Nd * log(s2) + ld + 0.5 * quad);
     const double trace_term = (kappa - sumA2) / (2.0 * s2);
     const double F = logmarg - trace_term;
+    // out[0]: F, or in mode SGP_SMALL_HMC the NUTS target (priors and log-Jacobians added) -- formed ONCE, here, so that the
+    // value-only launch and the gradient launch return the same bits (the value-only launch used to return the bare F in that mode)
+    double value = F;
+    if (tid == 0 && a.mode != 0) {
+      if (comp) {
+        // the NUTS target of experiments/co2_bayesian_sgpr_hmc.py:99-158: log-parameters ~ Normal(0, sd) (sampled in log
+        // space, no Jacobian), sigma ~ HalfNormal(1) log-transformed
+        double lp = F;
+        for (int k = 0; k < a.ncp; ++k) {
+          const double t = a.theta[k], sd = a.cp_sd[k];
+          lp += -0.5 * (t / sd) * (t / sd) - log(sd) - 0.9189385332046727;
+        }
+        const double tn = a.theta[a.ncp], sig2 = exp(2.0 * tn);
+        lp += -0.22579135264472741 - 0.5 * sig2 + tn;  // 0.5 log(2 / pi)
+        value = lp;
+      } else {
+        // NUTS target of models/bayesian_sgpr_hmc.py:60-71: ls ~ Gamma(2, 1), sig_f, sig_n ~ HalfCauchy(1), log transforms
+        double lp = F, sumth = 0.0;
+        const double c = log(2.0) - log(3.141592653589793);
+        for (int j = 0; j < d; ++j) {
+          const double l = hyp.ls[j];
+          lp += log(l) - l;
+          sumth += a.theta[j];
+        }
+        const double sf = exp(a.theta[d]), sn = exp(a.theta[d + 1]);
+        lp += (c - log1p(sf * sf)) + (c - log1p(sn * sn));
+        sumth += a.theta[d] + a.theta[d + 1];
+        value = lp + sumth;
+      }
+    }
     if (sm_ld(abortw) != 0 && tid == 0) *a.info = SGP_INFO_TIMEOUT;
     if (!a.want_grad) {
       if (tid == 0) {
-        a.out[0] = F;
+        a.out[0] = value;
         a.out[a.nh + 2] = logmarg;
         a.out[a.nh + 3] = trace_term;
       }
@@ -930,19 +960,15 @@ __device__ __forceinline__ void sm_eval_body(const SmallArgs& a, SmKernelShared<
           for (int p = 0; p < SGP_COMP_LEN; ++p) a.out[1 + p] = gsum[p];
           a.out[1 + SGP_COMP_LEN] = g_s2;
         } else {
-          // the NUTS target of experiments/co2_bayesian_sgpr_hmc.py:99-158: log-parameters ~ Normal(0, sd) (sampled in log
-          // space, no Jacobian), sigma ~ HalfNormal(1) log-transformed
-          double lp = F;
+          // chain rule of the NUTS target (its value: above)
           for (int k = 0; k < a.ncp; ++k) {
             const double t = a.theta[k], v = exp(t), sd = a.cp_sd[k];
             const double dF = gsum[a.cp_slot[k]];
-            lp += -0.5 * (t / sd) * (t / sd) - log(sd) - 0.9189385332046727;
             a.out[1 + k] = (a.cp_role[k] == 0 ? 2.0 * v * v * dF : v * dF) - t / (sd * sd);
           }
           const double tn = a.theta[a.ncp], sig2 = exp(2.0 * tn);
-          lp += -0.22579135264472741 - 0.5 * sig2 + tn;  // 0.5 log(2 / pi)
           a.out[1 + a.ncp] = 2.0 * sig2 * g_s2 - sig2 + 1.0;
-          a.out[0] = lp;
+          a.out[0] = value;
         }
       } else if (a.mode == 0) {
         a.out[0] = F;
@@ -950,21 +976,15 @@ __device__ __forceinline__ void sm_eval_body(const SmallArgs& a, SmKernelShared<
         a.out[1 + d] = g_sf2;
         a.out[2 + d] = g_s2;
       } else {
-        // NUTS target of models/bayesian_sgpr_hmc.py:60-71: ls ~ Gamma(2, 1), sig_f, sig_n ~ HalfCauchy(1), log transforms
-        double lp = F, sumth = 0.0;
-        const double c = log(2.0) - log(3.141592653589793);
+        // chain rule of the NUTS target (its value: above)
         for (int j = 0; j < d; ++j) {
           const double l = hyp.ls[j];
-          lp += log(l) - l;
-          sumth += a.theta[j];
           a.out[1 + j] = l * (gsum[j] + 1.0 / l - 1.0) + 1.0;
         }
         const double sf = exp(a.theta[d]), sn = exp(a.theta[d + 1]);
-        lp += (c - log1p(sf * sf)) + (c - log1p(sn * sn));
-        sumth += a.theta[d] + a.theta[d + 1];
         a.out[1 + d] = sf * (2.0 * sf * g_sf2 - 2.0 * sf / (1.0 + sf * sf)) + 1.0;
         a.out[2 + d] = sn * (2.0 * sn * g_s2 - 2.0 * sn / (1.0 + sn * sn)) + 1.0;
-        a.out[0] = lp + sumth;
+        a.out[0] = value;
       }
       a.out[a.nh + 2] = logmarg;
       a.out[a.nh + 3] = trace_term;
