@@ -17,6 +17,8 @@ SGP_MAX_INDUCING = 4096
 KERNEL_IDS = {"rbf": 0, "matern32": 1, "matern52": 2, "composite": 3}
 LIKELIHOOD_IDS = {"gaussian": 0, "bernoulli": 1, "bernoulli_logit": 2, "poisson": 3}  # SGP_LIK_* ("bernoulli" = the probit link)
 SGPMC_LIK_OUT_LEN = 3
+SGP_LIK_MULTICLASS_ROBUSTMAX = 4   # no likelihood_id argument takes it: sgp_sgpmc_mc_rows / sgp_sgpmc_mc_tail serve it
+SGP_MAX_CLASSES = 16
 COMP_LEN = 33  # SGP_COMP_LEN: doubles in a composite-kernel parameter block (include/sgp.h)
 OPT_CONTRACTION, OPT_ASM_OVERLAP, OPT_KFU_BUDGET_BYTES, OPT_COND_LIMIT, OPT_CU_BUDGET, OPT_TIMING, OPT_SHARED_DEVICE = range(7)
 OUT_F, OUT_LOGMARG, OUT_TRACE, OUT_LOGDETB, OUT_QUAD, OUT_TRW, OUT_S2BAR, OUT_KAPPABAR, OUT_LEN = range(9)
@@ -150,6 +152,12 @@ PROTOTYPES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_sgpmc_lik_workspace_bytes": (_sz, [_i32]),
     "sgp_sgpmc_lik_tail": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # ... with the multi-class robust-max likelihood: C latent GPs, V is C x M
+    "sgp_sgpmc_mc_rows_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "sgp_sgpmc_mc_rows": (_i32, [_vp, _i64, _vp, _vp, _i64, _dp, _dbl, _vp, _i32, _dbl, _i64, _i32, _i32, _i32, _vp, _i32,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_sgpmc_mc_workspace_bytes": (_sz, [_i32, _i32]),
+    "sgp_sgpmc_mc_tail": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # ... with a composite kernel, a white-noise term and a mean function
     "sgp_sgpmc_comp_rows_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "sgp_sgpmc_comp_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _dp, _dbl, _dbl, _vp, _i64, _i32, _i32, _i32, _vp, _i32,

@@ -144,7 +144,53 @@ SGP_LIK_HD void lik_poisson_log(double yb, double m, double vv, double& ell, dou
   gv = -0.5 * E;
 }
 
-constexpr int LIK_ID_MAX = 3;  // SGP_LIK_POISSON_LOG
+// SGP_LIK_MULTICLASS_ROBUSTMAX: C latent functions with means mu[0 .. C-1] and ONE shared variance vv, label yb in {0 .. C-1} (a double).
+//   p   = sum_i w_i prod_{c != y} Phi(x_i + (mu_y - mu_c) / sqrt vv)         (the probability that the labelled function is the largest)
+//   ell = p log(1 - eps) + (1 - p) log(eps / (C - 1))
+// The product is exp(sum log Phi): a saturated node underflows to 0, never to NaN.  gm[c] = d ell / d mu_c and gv = d ell / d vv are the
+// derivatives OF THAT SUM (the convention above).  gv has BOTH signs: negative where the labelled function leads, positive where it
+// trails -- a datum the model gets wrong wants more variance.  A label that is no integer of 0 .. C-1 gives NaN everywhere and is never
+// used as an index.  mu and gm must not overlap.
+SGP_LIK_HD void lik_robustmax(int C, double yb, const double* mu, double vv, double eps, const GHTable& gh, double& ell, double* gm,
+                              double& gv) {
+  int yi = -1;
+  if (yb >= 0.0 && yb < (double)C) {
+    yi = (int)yb;
+    if ((double)yi != yb) yi = -1;
+  }
+  if (yi < 0) {
+    const double bad = NAN;
+    ell = bad; gv = bad;
+    for (int c = 0; c < C; ++c) gm[c] = bad;
+    return;
+  }
+  const double isd = 1.0 / sqrt(vv), my = mu[yi];
+  for (int c = 0; c < C; ++c) gm[c] = 0.0;
+  double p = 0.0;
+  for (int i = 0; i < GH_N; ++i) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c)
+      if (c != yi) s += log_ndtr_dev(fma(my - mu[c], isd, gh.x[i]));
+    const double P = gh.w[i] * exp(s);
+    p += P;
+    for (int c = 0; c < C; ++c)
+      if (c != yi) gm[c] = fma(P, mills_dev(fma(my - mu[c], isd, gh.x[i])), gm[c]);  // d p / d delta_c so far, delta_c = (mu_y - mu_c) / sd
+  }
+  const double l1 = log1p(-eps), l0 = log(eps / (double)(C - 1)), kap = l1 - l0;
+  ell = p * l1 + (1.0 - p) * l0;
+  double sr = 0.0, srd = 0.0;
+  for (int c = 0; c < C; ++c) {
+    if (c == yi) continue;
+    const double r = gm[c];
+    sr += r;
+    srd = fma(r, (my - mu[c]) * isd, srd);
+    gm[c] = -kap * r * isd;
+  }
+  gm[yi] = kap * sr * isd;
+  gv = -0.5 * kap * srd * (isd * isd);
+}
+
+constexpr int LIK_ID_MAX = 3;  // SGP_LIK_POISSON_LOG (SGP_LIK_MULTICLASS_ROBUSTMAX has entry points of its own: sgp_sgpmc_mc.hip)
 
 // the likelihood `lik` (0..LIK_ID_MAX; the entry points check the range) at one datum
 SGP_LIK_HD void lik_eval(int lik, double yb, double m, double vv, double s2, const GHTable& gh, double& ell, double& gm, double& gv,

@@ -538,6 +538,71 @@ class HipEngine:
         _lib.check("sgp_sgpmc_lik_tail", st)
         return res
 
+    def sgpmc_mc_rows(self, X, y, Z, ls, sf2, V, kuu_linv, t_out, kernel="rbf", eps=1e-3, want_adjoints=False, want_moments=False):
+        """The SGPMC row pass of the multi-class robust-max likelihood (include/sgp.h: sgp_sgpmc_mc_rows).  ``V``: C x M on the device,
+        class-major; ``y``: the labels 0 .. C-1 as doubles, or None for the conditional moments only (prediction).  ``t_out`` (from
+        ``kfu_buffer``) holds T on return, with the adjoints the folded T_in = diag(dv) T - DMU V^T / (2 sf2) that
+        ``suffstats_bwd_factored(..., t_in=)`` takes with y = 0 and bbar = 0.
+
+        Returns dict(out = [sum ell | 0 | sum dv], dmu (C x N), dv (N); with the adjoints g (C x M), G (M x M); with ``want_moments`` or
+        ``y = None`` mu (C x N), var (N)).  Nothing is synchronised."""
+        N, d = X.shape
+        M = Z.shape[0]
+        self._chk(Z, "Z"), self._chk(kuu_linv, "kuu_linv"), self._chk(V, "V"), self._chk(t_out, "t_out")
+        if V.dim() != 2 or V.shape[1] != M:
+            raise ValueError("V must be C x M = ? x %d (got %s)" % (M, tuple(V.shape)))
+        Cn = int(V.shape[0])
+        if N > 0:
+            self._chk(X, "X")
+            if y is not None:
+                self._chk(y, "y")
+        if t_out.numel() < self.lib.sgp_kfu_len(N, M):
+            raise ValueError("t_out holds %d doubles, sgp_kfu_len(N, M) = %d" % (t_out.numel(), self.lib.sgp_kfu_len(N, M)))
+        if not 2 <= Cn <= _lib.SGP_MAX_CLASSES:
+            raise ValueError("V has %d rows: the class count must be 2 .. %d" % (Cn, _lib.SGP_MAX_CLASSES))
+        nbytes = self._cf.sgp_sgpmc_mc_rows_workspace_bytes(N, M, d, Cn)
+        if nbytes == 0:
+            raise ValueError("unsupported shape N=%d M=%d d=%d (the shard's K'_fu must fit one super-chunk)" % (N, M, d))
+        ws = self._workspace("sgpmc_mc_rows", nbytes)
+        res = {}
+        if y is not None:
+            res.update(out=self.empty(_lib.SGPMC_LIK_OUT_LEN), dmu=self.empty(Cn, N), dv=self.empty(N))
+        if want_moments or y is None:
+            res.update(mu=self.empty(Cn, N), var=self.empty(N))
+        if want_adjoints:
+            res.update(g=self.empty(Cn, M), G=self.empty(M, M))
+        st = self._cf.sgp_sgpmc_mc_rows(
+            self._ptr(X), d, self._ptr(y), self._ptr(Z), d, self._inv_ls(ls, d, kernel), float(sf2), self._ptr(V), Cn, float(eps), N, M, d,
+            _kernel_id(kernel), self._ptr(kuu_linv), 1 if want_adjoints else 0, self._ptr(res.get("out")), self._ptr(res.get("G")),
+            self._ptr(res.get("g")), self._ptr(res.get("dmu")), self._ptr(res.get("dv")), self._ptr(res.get("mu")),
+            self._ptr(res.get("var")), self._ptr(t_out), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_mc_rows", st)
+        return res
+
+    def sgpmc_mc_tail(self, rows, V, N, kuu_linv, with_adjoints=False, result=None, vbar_out=None):
+        """The M x M tail behind ``sgpmc_mc_rows`` (include/sgp.h: sgp_sgpmc_mc_tail) on its result ``rows``.
+
+        Returns dict(out = [F | sum ell | prior-of-V term | 0 | (sum dv) / N] in the head of ``buf``, info, buf, and with the adjoints
+        vbar, bbar (C x M each), Kuubar).  ``result`` / ``vbar_out`` (C M doubles) as for ``sgpmc_tail``.  Nothing is synchronised."""
+        Cn, M = int(V.shape[0]), int(V.shape[1])
+        self._chk(V, "V")
+        buf, out, info = result if result is not None else self.result_buffer()
+        res = {"out": out, "info": info, "buf": buf}
+        vbar = bbar = Kuubar = None
+        if with_adjoints:
+            if kuu_linv is None or "G" not in rows:
+                raise ValueError("sgpmc_mc_tail(with_adjoints=True) needs kuu_linv and the adjoints of sgpmc_mc_rows")
+            self._chk(kuu_linv, "kuu_linv")
+            vbar, bbar, Kuubar = vbar_out if vbar_out is not None else self.empty(Cn, M), self.empty(Cn, M), self.empty(M, M)
+            res.update(vbar=vbar, bbar=bbar, Kuubar=Kuubar)
+        ws = self._workspace("sgpmc_mc", self.lib.sgp_sgpmc_mc_workspace_bytes(M, Cn))
+        st = self.lib.sgp_sgpmc_mc_tail(
+            self._ptr(rows["out"]), self._ptr(rows.get("G")), self._ptr(rows.get("g")), self._ptr(V), Cn, int(N), M,
+            1 if with_adjoints else 0, self._ptr(out), self._ptr(vbar), self._ptr(bbar), self._ptr(Kuubar), self._ptr(kuu_linv),
+            self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_sgpmc_mc_tail", st)
+        return res
+
     def sgpmc_comp_rows(self, X, y, Z, block, white, s2, v, kuu_linv, t_out, likelihood="gaussian", mean=None, want_adjoints=False,
                         want_moments=False):
         """The SGPMC row pass for a composite kernel with a white-noise term and a mean function (include/sgp.h: sgp_sgpmc_comp_rows).

@@ -61,9 +61,11 @@ def _as_tensor(a):
     return t.to(torch.float64)
 
 
-def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed=None, warmup_iters=100, likelihood="gaussian"):
+def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed=None, warmup_iters=100, likelihood="gaussian",
+                  num_classes=None):
     """models/sgp_hmc.py:32-91.  ``data`` = (X_train, Y_train); returns ``(model, trace, wall_clock_secs)``.  ``likelihood``:
-    "gaussian" (the reference's), "bernoulli" (probit), "bernoulli_logit" or "poisson" (``targets.SgpmcTarget``).
+    "gaussian" (the reference's), "bernoulli" (probit), "bernoulli_logit", "poisson" or "multiclass" (robust-max over ``num_classes``
+    latent GPs, labels 0 .. C-1; C = max label + 1 when not given) (``targets.SgpmcTarget``).
 
     As the reference: (1) a warm-up, ``scipy.optimize.minimize(method="L-BFGS-B", jac=True, maxiter=warmup_iters)`` on -logp over
     every variable INCLUDING the inducing inputs (:54-55; gpflow.optimizers.Scipy's default method); (2) Z is frozen (:56); (3)
@@ -78,7 +80,8 @@ def train_sgp_hmc(data, Z_init, input_dims, tune, num_samples, engine=None, seed
         Z0 = Z0[:, None]
     if X.shape[1] != int(input_dims) or Z0.shape[1] != int(input_dims):
         raise ValueError("input_dims = %d, X has %d columns, Z_init has %d" % (int(input_dims), X.shape[1], Z0.shape[1]))
-    target = SgpmcTarget(X, Y, Z0, kernel="rbf", jitter=1e-5, engine=engine, likelihood=likelihood)   # SquaredExponential, jitter 1e-5 (:20, :36)
+    target = SgpmcTarget(X, Y, Z0, kernel="rbf", jitter=1e-5, engine=engine, likelihood=likelihood,   # SquaredExponential, jitter 1e-5 (:20, :36)
+                         **({"num_classes": num_classes} if likelihood == "multiclass" else {}))
     model = SgpmcModel(target)
     M, d, nd = target.M, target.d, target.ndim
     dev = target.engine.device
@@ -127,11 +130,29 @@ def train_sgp_hmc_composite(data, Z_init, kernel, tune, num_samples, priors=None
     return model, trace, wall_clock_secs
 
 
-def likelihood_moments(likelihood, mu, var):
+def _log_ndtr(z):
+    """log Phi(z), float64, finite down to where z^2 / 2 overflows (torch's routine: the host needs no erfcx of its own)."""
+    return torch.special.log_ndtr(torch.as_tensor(np.asarray(z, dtype=np.float64))).numpy()
+
+
+def likelihood_moments(likelihood, mu, var, eps=1e-3):
     """(E y, sd y) of y | f ~ likelihood with f ~ N(mu, var), elementwise:
     Bernoulli (y in {0, 1}): p and sqrt(p (1 - p)) with p = Phi(mu / sqrt(1 + var)) for the probit link, the 20-point Gauss-Hermite
-    mean of sigmoid(f) for the logit link; Poisson (log link): m = exp(mu + var / 2) and sqrt(m + (e^var - 1) m^2)."""
+    mean of sigmoid(f) for the logit link; Poisson (log link): m = exp(mu + var / 2) and sqrt(m + (e^var - 1) m^2).
+    "multiclass" (robust-max): ``mu`` is (.., C), the latent means of the C classes, ``var`` (..) their shared variance; returns the
+    class probabilities p_c = (1 - eps) P(c largest) + eps / (C - 1) (1 - P(c largest)), (.., C), with P(c largest) = sum_i w_i
+    prod_{k != c} Phi(x_i + (mu_c - mu_k) / sqrt var) on the 20-point rule of the device code, and sqrt(p (1 - p))."""
     mu, var = np.asarray(mu, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    if likelihood == "multiclass":
+        Cn = mu.shape[-1]
+        x, w = np.polynomial.hermite_e.hermegauss(20)
+        w = w / math.sqrt(2.0 * math.pi)
+        sd = np.sqrt(var)[..., None]
+        lp = _log_ndtr(x[:, None, None] + ((mu[..., :, None] - mu[..., None, :]) / sd[..., None])[..., None, :, :])   # (.., 20, c, k)
+        lp = lp * (1.0 - np.eye(Cn))                                                                                   # k != c
+        P = np.einsum("i,...ic->...c", w, np.exp(lp.sum(-1)))
+        p = (1.0 - eps) * P + eps / (Cn - 1) * (1.0 - P)
+        return p, np.sqrt(p * (1.0 - p))
     if likelihood == "poisson":
         m = np.exp(mu + 0.5 * var)
         return m, np.sqrt(m + np.expm1(var) * m * m)
@@ -168,6 +189,8 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
     n = min(int(n_draws), len(trace))
     if n <= 0:
         raise ValueError("the trace holds no draws")
+    if model.likelihood == "multiclass":
+        return _predict_multiclass(model, trace, Xs, n)
     LS = torch.zeros(M, M, dtype=torch.float64, device=e.device)
     f_means, y_stds = [], []
     for i in range(n):
@@ -185,6 +208,26 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
             y_stds.append(ys)
     f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
     return np.mean(f_means, axis=0), f_means, y_stds
+
+
+def _predict_multiclass(model, trace, Xs, n):
+    """Per draw one ``sgpmc_mc_rows`` call without labels on the test rows (the C latent means and their shared variance), then the class
+    probabilities on the host: ``(pred_mean (T x C), probs (draws x T x C), sqrt(p (1 - p)))``."""
+    e, t = model.engine, model.target
+    Z = model.Z
+    T, M = int(Xs.shape[0]), int(Z.shape[0])
+    t_buf = e.kfu_buffer(T, M)
+    probs = []
+    for i in range(n):
+        row = trace[i]
+        ls, sf2 = [float(v) for v in np.asarray(row["lengthscales"]).reshape(-1)], float(row["variance"])
+        V = torch.as_tensor(np.asarray(row["V"], dtype=np.float64).reshape(t.num_classes, M)).to(e.device).contiguous()
+        linv, _ = e.kuu_factor(e.kuu(Z, ls, sf2, model.jitter, model.kernel))
+        r = e.sgpmc_mc_rows(Xs, None, Z, ls, sf2, V, linv, t_buf, model.kernel, t.eps)
+        mu, var = r["mu"].detach().to("cpu").numpy().T, np.maximum(r["var"].detach().to("cpu").numpy(), sf2 * 2.0 ** -40)
+        probs.append(likelihood_moments("multiclass", mu, var, t.eps)[0])
+    probs = np.stack(probs)
+    return probs.mean(0), probs, np.sqrt(probs * (1.0 - probs))
 
 
 def _predict_composite(model, trace, X_test, n_draws):

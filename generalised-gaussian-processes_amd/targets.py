@@ -325,6 +325,23 @@ def _softplus_inv(c):
     return c + math.log(-math.expm1(-c))
 
 
+def multiclass_labels(y, num_classes=None):
+    """The class count C of a label vector for the robust-max likelihood: the labels must be integers 0 .. C-1, C = max + 1 unless
+    ``num_classes`` says more (a class may have no datum); 2 <= C <= 16 (SGP_MAX_CLASSES).  Anything else raises ValueError."""
+    yh = torch.as_tensor(y).detach().to("cpu", torch.float64).reshape(-1)
+    if yh.numel() == 0 and num_classes is None:
+        raise ValueError("no labels and no num_classes: the class count cannot be inferred")
+    if yh.numel() and not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
+        raise ValueError("multi-class labels must be the integers 0 .. C-1")
+    top = int(yh.max()) + 1 if yh.numel() else 0
+    C = top if num_classes is None else int(num_classes)
+    if num_classes is not None and (C != num_classes or C < top):
+        raise ValueError("num_classes = %r does not hold the labels 0 .. %d" % (num_classes, top - 1))
+    if not 2 <= C <= 16:
+        raise ValueError("the class count must be 2 .. 16 (got %d)" % C)
+    return C
+
+
 class SgpmcTarget:
     """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values together (GPflow's ``SGPMC``, with a
     Gaussian likelihood models/sgp_hmc.py:38-43), q = [x_var | x_ls (d) | x_noise | v (M)] unconstrained, ndim = d + 2 + M.
@@ -349,11 +366,19 @@ class SgpmcTarget:
     ``sgpmc_lik_tail`` -> ``suffstats_bwd_factored(t_in = diag(dv) T, y = dmu, Cw = -2 I, s2 = 1, bbar = L^-T v)`` -> ``kuu_bwd``
     (include/sgp.h states the density, its adjoints and why pass 2 needs no new kernel), again with one device-to-host copy: the
     diagonal term of dF/d variance, sum_n dv_n, comes back in that copy and is added on the host, where pass 2's ``kappabar`` argument
-    would have needed it before the launch."""
+    would have needed it before the launch.
 
-    LIKELIHOODS = ("gaussian", "bernoulli", "bernoulli_logit", "poisson")
+    ``likelihood="multiclass"``: the robust-max likelihood over ``num_classes`` = C latent GPs that share the kernel and Z (labels are
+    the integers 0 .. C-1; C = max + 1 when ``num_classes`` is None; 2 <= C <= 16), with ``robustmax_eps`` the probability mass spread
+    over the wrong classes.  q = [x_var | x_ls (d) | vec(V) class-major], ndim = d + 1 + M C, ``constrain()["V"]`` is (C, M); priors
+    and transforms of the theta entries unchanged.  One evaluation is ``kuu`` -> ``kuu_factor`` -> ``sgpmc_mc_rows`` ->
+    ``sgpmc_mc_tail`` -> ``suffstats_bwd_factored(t_in = diag(dv) T - DMU V^T / (2 sf2), y = 0, Cw = -2 I, s2 = 1, bbar = 0)`` ->
+    ``kuu_bwd``: ONE pass 2 whatever C is (include/sgp.h, the sgp_sgpmc_mc_rows section), one device-to-host copy."""
 
-    def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None, likelihood="gaussian"):
+    LIKELIHOODS = ("gaussian", "bernoulli", "bernoulli_logit", "poisson", "multiclass")
+
+    def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None, likelihood="gaussian", num_classes=None,
+                 robustmax_eps=1e-3):
         from .core import _world
         if likelihood not in self.LIKELIHOODS:
             raise ValueError("SgpmcTarget takes the likelihoods %s (got %r)" % (", ".join(self.LIKELIHOODS), likelihood))
@@ -383,6 +408,14 @@ class SgpmcTarget:
             yh = self.y.detach().to("cpu")
             if not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
                 raise ValueError("Poisson counts must be non-negative integers")
+        self.n_latent = 1                                     # latent GPs = columns of whitened inducing values
+        self.eps = float(robustmax_eps)
+        if likelihood == "multiclass":
+            self.n_latent = self.num_classes = multiclass_labels(self.y, num_classes)
+            if not 0.0 < self.eps < 1.0:
+                raise ValueError("robustmax_eps must lie in (0, 1) (got %r)" % (robustmax_eps,))
+        elif num_classes is not None:
+            raise ValueError("num_classes belongs to likelihood='multiclass' (got likelihood=%r)" % (likelihood,))
         self.n_theta = self.X.shape[1] + (2 if likelihood == "gaussian" else 1)   # [x_var | x_ls (d) | x_noise (Gaussian only)]
         self.kernel = kernel
         self.jitter = float(jitter)
@@ -403,14 +436,14 @@ class SgpmcTarget:
             raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
         self.Z = Z
         self.M = int(Z.shape[0])
-        self.ndim = self.n_theta + self.M
+        self.ndim = self.n_theta + self.M * self.n_latent
 
     def start(self):
         """GPflow's defaults as the reference sets them (models/sgp_hmc.py:36): variance log(2)^2, lengthscales log 2, likelihood
         variance 1, v = 0."""
         ln2 = math.log(2.0)
         noise = [_softplus_inv(1.0 - _SGPMC_NOISE_FLOOR)] if self.likelihood == "gaussian" else []
-        return [_softplus_inv(ln2 * ln2)] + [_softplus_inv(ln2)] * self.d + noise + [0.0] * self.M
+        return [_softplus_inv(ln2 * ln2)] + [_softplus_inv(ln2)] * self.d + noise + [0.0] * (self.M * self.n_latent)
 
     def constrain(self, q):
         """The constrained values of a position; ``noise_variance`` only with the Gaussian likelihood."""
@@ -420,6 +453,8 @@ class SgpmcTarget:
         if self.likelihood == "gaussian":
             c["noise_variance"] = _SGPMC_NOISE_FLOOR + _softplus(x[1 + d])
         c["V"] = np.asarray(x[self.n_theta:], dtype=np.float64)
+        if self.likelihood == "multiclass":
+            c["V"] = c["V"].reshape(self.num_classes, self.M)   # class-major
         return c
 
     def _t_for(self):
@@ -469,12 +504,34 @@ class SgpmcTarget:
                                  want_gz=want_gz, out=g, t_in=t_keep)
         return res["Kuubar"]
 
+    def _zeros(self, n):
+        z = self.__dict__.get("_zeros_keep")
+        if z is None or z.numel() < n:
+            z = self._zeros_keep = torch.zeros(max(n, 1), dtype=torch.float64, device=self.engine.device)
+        return z[:n]
+
+    def _chain_mc(self, ls, sf2, s2, v, linv, result, vbar_kw, g, want_grad, want_gz):
+        """The same for the multi-class robust-max likelihood: V is C x M, and ONE pass 2 takes the N-side gradient of all classes from
+        the folded T_in = diag(dv) T - DMU V^T / (2 sf2) the row pass leaves, with y := 0, bbar := 0, Cw := -2 I, s2 := 1."""
+        e, Z = self.engine, self.Z
+        t_keep = self._t_for()
+        V = v.view(self.num_classes, self.M)
+        rows = e.sgpmc_mc_rows(self.X, self.y, Z, ls, sf2, V, linv, t_keep, self.kernel, self.eps, want_adjoints=want_grad)
+        self.last_pass1 = "sgpmc_mc_rows"
+        res = e.sgpmc_mc_tail(rows, V, self.N, linv, with_adjoints=want_grad, result=result, **vbar_kw)
+        if not want_grad:
+            return None
+        e.suffstats_bwd_factored(self.X, self._zeros(self.N), Z, ls, sf2, linv, self._cw(), 1.0, self._zeros(self.M), 0.0, self.kernel,
+                                 want_gz=want_gz, out=g, t_in=t_keep)
+        return res["Kuubar"]
+
     def _eval(self, q, want_grad, want_gz=False):
         x = as_floats(q)
         d, M, e, nt = self.d, self.M, self.engine, self.n_theta
         gaussian = self.likelihood == "gaussian"
         if len(x) != self.ndim:
-            raise ValueError("the position has %d entries, expected %d theta + M = %d" % (len(x), nt, self.ndim))
+            raise ValueError("the position has %d entries, expected %d theta + %d inducing values = %d" % (len(x), nt, self.ndim - nt,
+                                                                                                         self.ndim))
         bad = (-math.inf, [0.0] * self.ndim if want_grad else None, None)
         if not all(math.isfinite(t) for t in x) or not all(abs(t) < 700.0 for t in x[:nt]):
             return bad
@@ -486,7 +543,8 @@ class SgpmcTarget:
             raise ValueError("the engine has no kfu_buffer: SgpmcTarget(likelihood=%r) needs the caller-owned T" % (self.likelihood,))
         self.n_evals += 1
         ng = d + 1 + (M * d if want_gz else 0)
-        extra = ng + M if want_grad else 0
+        nv = M * self.n_latent
+        extra = ng + nv if want_grad else 0
         result = e.result_buffer(extra)
         buf = result[0]
         head = buf.numel() - extra
@@ -494,7 +552,7 @@ class SgpmcTarget:
         linv, _ = e.kuu_factor(Kuu, info=result[2])   # the evaluation's status word is the K_uu status: the tails factor nothing
         v = torch.tensor(x[nt:], dtype=torch.float64).to(e.device)
         g = buf[head:head + ng] if want_grad else None
-        chain = self._chain_gaussian if gaussian else self._chain_lik
+        chain = self._chain_gaussian if gaussian else (self._chain_mc if self.likelihood == "multiclass" else self._chain_lik)
         Kuubar = chain(ls, sf2, s2, v, linv, result, {"vbar_out": buf[head + ng:]} if want_grad else {}, g, want_grad, want_gz)
         if want_grad:
             e.kuu_bwd(self.Z, ls, sf2, Kuubar, g, self.kernel, want_gz=want_gz)
@@ -518,7 +576,7 @@ class SgpmcTarget:
         # dF/d variance, dF/d lengthscales and, Gaussian, dF/d s2 (SGP_SGPMC_OUT_S2BAR).  Non-conjugate: + sum_n dv_n = N out[4] on
         # dF/d variance (k(x_n, x_n) = variance), which pass 2's host scalar kappabar could not carry without a second host copy
         dF = [gh[d]] + gh[:d] + [float(o[3])] if gaussian else [gh[d] + float(o[4]) * self.N] + gh[:d]
-        grad = [(dF[k] + 1.0 / cons[k] - 1.0) * sig[k] + (1.0 - sig[k]) for k in range(nt)] + hl[head + ng:head + ng + M]
+        grad = [(dF[k] + 1.0 / cons[k] - 1.0) * sig[k] + (1.0 - sig[k]) for k in range(nt)] + hl[head + ng:head + ng + nv]
         if not all(math.isfinite(t) for t in grad):
             return bad
         gz = buf[head + d + 1:head + ng].reshape(M, d) if want_gz else None

@@ -546,6 +546,46 @@ int sgp_sgpmc_lik_tail(const double* rows_out, const double* G, const double* g,
                        double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
                        sgp_stream_t stream);
 
+/* ---- SGPMC with the multi-class robust-max likelihood ------------------------------------------------------------------------------
+ * C latent GPs share one kernel and one Z ([UPSTREAM] GPflow's convention for MultiClass(RobustMax): one kernel, num_latent_gps = C, as
+ * recalled; nothing was checked against it).  Whitened inducing values V = [v_1 .. v_C], v_c ~ N(0, I), labels y_n in {0 .. C-1}:
+ *   mu_nc = a_n.v_c     var_n = sf2 - |a_n|^2  (shared by all classes; below 2^-40 sf2: raised to it, dv_n = 0)
+ *   p_n   = sum_i w_i prod_{c != y_n} Phi(x_i + (mu_{n,y_n} - mu_nc) / sqrt var_n)          (the 20-point Gauss-Hermite rule)
+ *   ell_n = p_n log(1 - eps) + (1 - p_n) log(eps / (C - 1))
+ *   F(V, theta) = sum_n ell_n - 1/2 sum_c v_c.v_c - (M C / 2) log(2 pi)
+ * dmu_nc = d ell_n / d mu_nc and dv_n = d ell_n / d var_n are the derivatives of that quadrature sum.  dv_n HAS BOTH SIGNS here (a datum
+ * the model gets wrong wants more variance), so G is formed as the difference of two row-scaled contractions, over the rows with
+ * dv > 0 and over those with dv < 0; nothing is clamped.
+ *   g_c = sum_n dmu_nc a_n     G = sum_n dv_n a_n a_n^T     vbar_c = g_c - v_c     bbar_c = w_c = L^-T v_c
+ *   Kuubar = L^-T (G - sum_c sym(low(v_c g_c^T))) L^-1
+ *   Kfubar row n = sum_c dmu_nc w_c^T - 2 dv_n (sf2 T_n) L^-1                              dF / d k(x_n, x_n) = dv_n
+ * Pass 2 takes that row from ONE sgp_suffstats_bwd_factored_ex call: with L^T w_c = v_c,
+ *   T_in = diag(dv) T - (1 / (2 sf2)) DMU V^T,   Cw := -2 I,  s2 := 1,  y := 0,  bbar := 0,  kappabar := 0
+ * gives sf2 T_in Cw L^-1 = -2 dv (sf2 T) L^-1 + DMU V^T L^-1.  T_in is what T_out holds after a call with adjoints.
+ *
+ * sgp_sgpmc_mc_rows: prologue, assembly and T = K'_fu L^-T exactly as sgp_sgpmc_lik_rows (stationary kernels only), then ONE pass over
+ * T forms the C means and the variance of every datum (V staged through LDS by column blocks) and runs the likelihood.
+ *   y (DEVICE, N doubles holding the labels 0 .. C-1); a label outside that range, or no integer, makes that datum's ell NaN and is
+ *     never used as an address.  y == NULL: moments only (prediction) -- mu and var are written and nothing else.
+ *   V (DEVICE, C x M, class-major);  g (C x M);  dmu, mu (C x N, class-major);  dv, var (N; var as formed, not floored)
+ *   out (DEVICE, SGP_SGPMC_LIK_OUT_LEN) = [sum ell | 0 | sum dv];  G (M x M, ld M);  mu, var optional when y is given
+ *   want_adjoints != 0: g, G, and T_out = T_in above (zero padding); 0: T_out = T.
+ * SGP_ERR_ARG: C outside 2 .. SGP_MAX_CLASSES, eps outside (0, 1), a NULL required pointer, SGP_KERNEL_COMPOSITE, adjoints without G, g or
+ * y; SGP_ERR_DIM, SGP_ERR_WORKSPACE as sgp_sgpmc_lik_rows; all before any launch.  N = 0 is legal.  Every sum runs in a fixed order.
+ * sgp_sgpmc_mc_tail: out in the SGP_SGPMC_OUT_* layout with _PRIOR = -1/2 sum_c v_c.v_c - (M C / 2) log(2 pi), _S2BAR = 0; with the
+ * adjoints vbar, bbar (C x M each) and Kuubar (M x M, ld M).                                                                        */
+#define SGP_LIK_MULTICLASS_ROBUSTMAX 4 /* served by the two entry points below only: every likelihood_id argument answers SGP_ERR_ARG to it */
+#define SGP_MAX_CLASSES 16
+size_t sgp_sgpmc_mc_rows_workspace_bytes(int64_t N, int M, int d, int C);
+int sgp_sgpmc_mc_rows(const double* X, int64_t ldx, const double* y, const double* Z, int64_t ldz, const double* inv_ls, double sf2,
+                      const double* V, int C, double eps, int64_t N, int M, int d, int kernel_id, const double* kuu_linv,
+                      int want_adjoints, double* out, double* G, double* g, double* dmu, double* dv, double* mu, double* var,
+                      double* T_out, void* ws, size_t ws_bytes, sgp_stream_t stream);
+size_t sgp_sgpmc_mc_workspace_bytes(int M, int C);
+int sgp_sgpmc_mc_tail(const double* rows_out, const double* G, const double* g, const double* V, int C, int64_t N, int M,
+                      int with_adjoints, double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv, void* ws,
+                      size_t ws_bytes, sgp_stream_t stream);
+
 /* ---- SGPMC with a composite kernel, a white-noise term and a mean function ----------------------------------------------------------
  * The model of the reference's experiments/co2_sgpmc.py: a sum-of-products covariance (`block`, HOST, SGP_COMP_LEN doubles) plus
  * white noise of variance `white` >= 0, and a mean function m(x).  [UPSTREAM] GPflow's White.K(Z, X) is 0 for two different sets of
