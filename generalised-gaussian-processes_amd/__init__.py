@@ -9,7 +9,7 @@ from .composite import (CO2_LOG_PRIOR_SD, CO2_SGPMC_PRIORS, CompositeBayesianSpa
 from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
 from . import datasets, experiment_tools  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
-                      MultivariateNormal, PoissonLikelihood, RBFKernel, ScaleKernel, ZeroMean, settings)
+                      MultivariateNormal, PoissonLikelihood, RBFKernel, RobustMaxLikelihood, ScaleKernel, ZeroMean, settings)
 from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_device  # noqa: F401
 from .metrics import negative_log_predictive_mixture_density, nlpd, nlpd_marginal, nlpd_mixture, rmse  # noqa: F401
 from .ml2 import Ml2Result, fit_ml2, identification_data, lml_surface  # noqa: F401

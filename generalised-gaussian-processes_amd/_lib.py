@@ -212,6 +212,12 @@ PROTOTYPES = {
     "sgp_mixture_predict_zs": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _dp, _dp, _dp, _dbl, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_svgp_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _vp, _i32, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the multi-class (robust-max) SVGP bound: C classes, m is C x M, LS is C x M x M
+    "sgp_svgp_mc_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "sgp_svgp_mc_elbo": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _vp, _i32, _dbl, _i64, _i32, _i32, _i32, _i32,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgp_svgp_mc_predict": (_i32, [_vp, _i64, _i64, _vp, _i64, _dp, _dbl, _dbl, _vp, _vp, _i32, _dbl, _i32, _i32, _i32,
+                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgp_gauss_hermite": (_i32, [_i32, _dp, _dp]),
     # the exact GP marginal likelihood and its predictive (GPR_HMC)
     "sgp_exact_workspace_bytes": (_sz, [_i64, _i32, _i32]),

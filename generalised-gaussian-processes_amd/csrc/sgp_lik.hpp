@@ -212,4 +212,82 @@ SGP_LIK_HD void lik_eval_floored(int lik, double yb, double m, double vv, double
   if (floored) gv = 0.0;
 }
 
+// SGP_LIK_MULTICLASS_ROBUSTMAX with one variance PER CLASS (the multi-class SVGP bound, sgp_svgp_mc.hip: every class has a q(u_c) of
+// its own).  Class c's mean and variance are mu[c * stride], var[c * stride] (stride 1: plain arrays; the device keeps them class-major,
+// stride = the padded minibatch).  With z_ic = (mu_y + sqrt(v_y) x_i - mu_c) / sqrt(v_c) = a_c + b_c x_i:
+//   P[i] = w_i prod_{c != y} Phi(z_ic),  returned: p = sum_i P[i]   (the probability that function y is the largest)
+// A variance below var_floor is raised to it (lik_eval_floored's rule).  yi must be a class index.
+SGP_LIK_HD double robustmax_pv_nodes(int C, int yi, const double* mu, const double* var, long stride, double var_floor,
+                                     const GHTable& gh, double* P /* GH_N */) {
+  const double vy = var[yi * stride] < var_floor ? var_floor : var[yi * stride];
+  const double sdy = sqrt(vy), my = mu[yi * stride];
+  for (int i = 0; i < GH_N; ++i) P[i] = 0.0;
+  for (int c = 0; c < C; ++c) {
+    if (c == yi) continue;
+    const double vc = var[c * stride] < var_floor ? var_floor : var[c * stride];
+    const double isd = 1.0 / sqrt(vc), a = (my - mu[c * stride]) * isd, b = sdy * isd;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < GH_N; ++i) P[i] += log_ndtr_dev(fma(b, gh.x[i], a));
+  }
+  double p = 0.0;
+  for (int i = 0; i < GH_N; ++i) {
+    P[i] = gh.w[i] * exp(P[i]);
+    p += P[i];
+  }
+  return p;
+}
+
+//   ell = p log(1 - eps) + (1 - p) log(eps / (C - 1)),  kappa = log(1 - eps) - log(eps / (C - 1)),  r_ic = P_i phi(z_ic) / Phi(z_ic),
+//   R_c = sum_i r_ic,  X_c = sum_i r_ic x_i:
+//   gm[c] = -kappa R_c / sqrt(v_c)                       gm[y] = kappa sum_c R_c / sqrt(v_c)
+//   gv[c] = -kappa (a_c R_c + b_c X_c) / (2 v_c)         gv[y] = kappa sum_c X_c / (2 sqrt(v_y) sqrt(v_c))
+// -- the derivatives OF THAT SUM, as above; with all variances equal gm is lik_robustmax's and sum_c gv[c] its gv.  The gv of a floored
+// variance is 0.  A label that is no integer of 0 .. C-1 gives NaN everywhere and is never used as an index.  gm / gv use the same stride;
+// gm may be mu and gv may be var (class c's inputs are read before its outputs are written, class y's before any).
+SGP_LIK_HD void lik_robustmax_pv(int C, double yb, const double* mu, const double* var, long stride, double var_floor, double eps,
+                                 const GHTable& gh, double& ell, double* gm, double* gv) {
+  int yi = -1;
+  if (yb >= 0.0 && yb < (double)C) {
+    yi = (int)yb;
+    if ((double)yi != yb) yi = -1;
+  }
+  if (yi < 0) {
+    const double bad = NAN;
+    ell = bad;
+    for (int c = 0; c < C; ++c) gm[c * stride] = gv[c * stride] = bad;
+    return;
+  }
+  const bool floored_y = var[yi * stride] < var_floor;
+  const double vy = floored_y ? var_floor : var[yi * stride];
+  const double sdy = sqrt(vy), my = mu[yi * stride];
+  double P[GH_N];
+  const double p = robustmax_pv_nodes(C, yi, mu, var, stride, var_floor, gh, P);
+  const double l1 = log1p(-eps), l0 = log(eps / (double)(C - 1)), kap = l1 - l0;
+  ell = p * l1 + (1.0 - p) * l0;
+  double sr = 0.0, sx = 0.0;
+  for (int c = 0; c < C; ++c) {
+    if (c == yi) continue;
+    const bool floored = var[c * stride] < var_floor;
+    const double vc = floored ? var_floor : var[c * stride];
+    const double isd = 1.0 / sqrt(vc), a = (my - mu[c * stride]) * isd, b = sdy * isd;
+    double R = 0.0, X = 0.0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < GH_N; ++i) {
+      const double r = P[i] * mills_dev(fma(b, gh.x[i], a));
+      R += r;
+      X = fma(r, gh.x[i], X);
+    }
+    gm[c * stride] = -kap * R * isd;
+    gv[c * stride] = floored ? 0.0 : -0.5 * kap * fma(a, R, b * X) * (isd * isd);
+    sr = fma(R, isd, sr);
+    sx = fma(X, isd, sx);
+  }
+  gm[yi * stride] = kap * sr;
+  gv[yi * stride] = floored_y ? 0.0 : 0.5 * kap * sx / sdy;
+}
+
 }  // namespace sgp

@@ -1209,6 +1209,65 @@ class HipEngine:
         _lib.check("sgp_svgp_predict", st)
         return mean, var, info
 
+    # ------------------------------------------------------------------ multi-class (robust-max) SVGP bound
+    def svgp_mc_elbo(self, Xb, yb, Z, ls, sf2, m, LS, N_total, eps=1e-3, jitter=1e-6, kernel="rbf", with_grads=False):
+        """One minibatch of the multi-class SVGP bound (include/sgp.h: sgp_svgp_mc_elbo).  ``yb``: labels 0 .. C-1 as doubles, ``m``: C x M,
+        ``LS``: C x M x M on the device.  Returns dict(out [4] = [bound per datum | sum E log p | KL | status word], info, and with
+        ``with_grads`` g_m [C, M], g_LS [C, M, M], g_Z [M, d], g_ls [d], g_sf2 [1]); device tensors, nothing synchronised."""
+        B, d = Xb.shape
+        Cn, M = m.shape
+        if LS.shape != (Cn, M, M) or Z.shape != (M, d):
+            raise ValueError("svgp_mc_elbo: m is C x M, LS is C x M x M, Z is M x d")
+        for t, n in ((Xb, "Xb"), (yb, "yb"), (Z, "Z"), (m, "m"), (LS, "LS")):
+            self._chk(t, n)
+        out = self.empty(4)
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        res = {"out": out, "info": info}
+        g = {}
+        if with_grads:
+            g = {"g_m": self.empty(Cn, M), "g_LS": self.empty(Cn, M, M), "g_Z": self.empty(M, d), "g_ls": self.empty(d),
+                 "g_sf2": self.empty(1)}
+            res.update(g)
+        nbytes = self.lib.sgp_svgp_mc_workspace_bytes(B, M, d, Cn)
+        if nbytes == 0:
+            raise ValueError("unsupported multi-class SVGP shape B=%d M=%d d=%d C=%d" % (B, M, d, Cn))
+        ws = self._workspace("svgp_mc", nbytes)
+        st = self._cf.sgp_svgp_mc_elbo(
+            self._ptr(Xb), d, self._ptr(yb), B, self._ptr(Z), d, self._inv_ls(ls, d), float(sf2), float(jitter), self._ptr(m),
+            self._ptr(LS), Cn, float(eps), int(N_total), M, d, _kernel_id(kernel), 1 if with_grads else 0, self._ptr(out),
+            self._ptr(g.get("g_m")), self._ptr(g.get("g_LS")), self._ptr(g.get("g_Z")), self._ptr(g.get("g_ls")),
+            self._ptr(g.get("g_sf2")), self._ptr(info), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_svgp_mc_elbo", st)
+        return res
+
+    SVGP_MC_PREDICT_CHUNK = 4096  # test rows per sgp_svgp_mc_predict call (the workspace holds C x Mp x rows)
+
+    def svgp_mc_predict(self, Xs, Z, ls, sf2, m, LS, eps=1e-3, jitter=1e-6, kernel="rbf", want_probs=True):
+        """Latent means and variances (T x C each) of the C classes at the rows ``Xs`` and, with ``want_probs``, the class probabilities
+        (T x C) of the robust-max likelihood, all formed on the device (sgp_svgp_mc_predict).  Returns (mean, var, probs or None, info)."""
+        T, d = Xs.shape
+        Cn, M = m.shape
+        for t, n in ((Xs, "Xs"), (Z, "Z"), (m, "m"), (LS, "LS")):
+            self._chk(t, n)
+        mean, var = self.empty(T, Cn), self.empty(T, Cn)
+        probs = self.empty(T, Cn) if want_probs else None
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        for t0 in range(0, T, self.SVGP_MC_PREDICT_CHUNK):
+            tn = min(self.SVGP_MC_PREDICT_CHUNK, T - t0)
+            nbytes = self.lib.sgp_svgp_mc_workspace_bytes(tn, M, d, Cn)
+            if nbytes == 0:
+                raise ValueError("unsupported multi-class SVGP shape T=%d M=%d d=%d C=%d" % (tn, M, d, Cn))
+            ws = self._workspace("svgp_mc", nbytes)
+            mc, vc = self.empty(Cn, tn), self.empty(Cn, tn)
+            st = self._cf.sgp_svgp_mc_predict(
+                self._ptr(Xs[t0:t0 + tn]), d, tn, self._ptr(Z), d, self._inv_ls(ls, d), float(sf2), float(jitter), self._ptr(m),
+                self._ptr(LS), Cn, float(eps), M, d, _kernel_id(kernel), self._ptr(mc), self._ptr(vc),
+                self._ptr(probs[t0:t0 + tn]) if want_probs else None, self._ptr(info), self._ptr(ws), ws.numel(), self._stream())
+            _lib.check("sgp_svgp_mc_predict", st)
+            mean[t0:t0 + tn] = mc.T
+            var[t0:t0 + tn] = vc.T
+        return mean, var, probs, info  # every chunk factors the same K_uu: one status word says it all
+
     # ------------------------------------------------------------------ stand-alone M x M entry points
     def chol_lower(self, A: torch.Tensor):
         M = A.shape[0]

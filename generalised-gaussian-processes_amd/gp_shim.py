@@ -182,6 +182,48 @@ class PoissonLikelihood(nn.Module):
         return torch.exp(dist.loc + 0.5 * dist.variance)
 
 
+def robustmax_class_probs(mean, var, eps):
+    """probs[t][c] = (1 - eps) P(c largest) + eps / (C - 1) (1 - P(c largest)) for independent latents N(mean[t][c], var[t][c]):
+    P(c largest) = sum_i w_i prod_{c' != c} Phi((mean_c + sqrt(var_c) x_i - mean_c') / sqrt(var_c')) by the 20-point Gauss-Hermite rule
+    the bound uses (what sgp_svgp_mc_predict forms on the device, here in torch for latents that are already on the host)."""
+    import numpy as np
+    x, w = np.polynomial.hermite_e.hermegauss(20)
+    x = torch.as_tensor(x, dtype=mean.dtype, device=mean.device)
+    w = torch.as_tensor(w / (2.0 * np.pi) ** 0.5, dtype=mean.dtype, device=mean.device)
+    C = mean.shape[-1]
+    sd = torch.sqrt(var.clamp_min(torch.finfo(mean.dtype).tiny))
+    f = mean[..., :, None] + sd[..., :, None] * x                                      # T x C x 20: class c's value at node i
+    z = (f[..., :, None, :] - mean[..., None, :, None]) / sd[..., None, :, None]       # T x C (label) x C' (other) x 20
+    lp = torch.special.log_ndtr(z)
+    lp = lp * (1.0 - torch.eye(C, dtype=mean.dtype, device=mean.device))[:, :, None]   # the label's own factor is left out
+    p = torch.exp(lp.sum(-2)) @ w
+    return (1.0 - eps) * p + eps / (C - 1) * (1.0 - p)
+
+
+class RobustMaxLikelihood(nn.Module):
+    """Multi-class robust-max likelihood over C latent functions: the label is the arg-max with probability 1 - epsilon, any other
+    class with epsilon / (C - 1); labels are the integers 0 .. C-1; no noise parameter.  ([UPSTREAM] GPflow's MultiClass(RobustMax),
+    as recalled.)  Calling it on latents with (T x C) mean and variance returns the T x C class probabilities."""
+    name = "multiclass"
+
+    def __init__(self, num_classes, epsilon=1e-3):
+        super().__init__()
+        if int(num_classes) != num_classes or not 2 <= int(num_classes) <= 16:
+            raise ValueError("the class count must be 2 .. 16 (got %r)" % (num_classes,))
+        if not 0.0 < float(epsilon) < 1.0:
+            raise ValueError("epsilon must lie in (0, 1) (got %r)" % (epsilon,))
+        self.num_classes = int(num_classes)
+        self.epsilon = float(epsilon)
+
+    def forward(self, dist):
+        return self(dist)
+
+    def __call__(self, dist):
+        if dist.loc.dim() != 2 or dist.loc.shape[-1] != self.num_classes:
+            raise ValueError("RobustMaxLikelihood(%d) needs latents of shape T x %d" % (self.num_classes, self.num_classes))
+        return robustmax_class_probs(dist.loc, dist.variance, self.epsilon)
+
+
 class InducingPointKernel(nn.Module):
     def __init__(self, base_kernel, inducing_points, likelihood):
         super().__init__()

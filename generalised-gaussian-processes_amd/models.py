@@ -24,7 +24,7 @@ from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, few
 from .gp_shim import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, LazyPredictive,
                       MultivariateNormal, RBFKernel, ScaleKernel, TrainPrior, ZeroMean)
 from .hmc import Trace, next_seed, sample_nuts, sample_nuts_device, trace_summary
-from .targets import EXACT_MAX_N, ExactHmcTarget, HmcTarget, JointHmcTarget
+from .targets import EXACT_MAX_N, ExactHmcTarget, HmcTarget, JointHmcTarget, multiclass_labels
 
 FULL_COV_MAX_T = 4096  # predictive covariance is T x T; beyond this only mean / variance are formed
 
@@ -584,6 +584,36 @@ class _SVGPBatchBoundFn(torch.autograd.Function):
         return g_theta, gZ if n[1] else None, gm if n[2] else None, gLS if n[3] else None, None, None, None
 
 
+class _SVGPMcBoundFn(torch.autograd.Function):
+    """ELBO per datum of one minibatch under the multi-class robust-max likelihood: forward and the whole reverse pass run in
+    sgp_svgp_mc_elbo (m: C x M, LS: C x M x M; the launch count does not depend on C).  The hyper-parameters stay on the host."""
+
+    @staticmethod
+    def forward(ctx, ls, sf2, Z, m, LS, model, xb, yb):
+        eng = model._engine_obj()
+        need = any(ctx.needs_input_grad[:5])
+        res = eng.svgp_mc_elbo(xb, yb, Z.detach().contiguous(), ls.detach().reshape(-1).tolist(), float(sf2), m.detach().contiguous(),
+                               LS.detach().contiguous(), model.num_data, eps=model.likelihood.epsilon, jitter=model.jitter,
+                               kernel=model.covar_module.base_kernel.kernel_name, with_grads=need)
+        host = res["out"].to("cpu")  # one copy brings the bound and the factorization's status word
+        _raise_on_info(int(host[3]))
+        ctx.res = res if need else None
+        ctx.meta = [(t.shape, t.device) for t in (ls, sf2, Z, m, LS)]
+        return host[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        r = ctx.res
+        outs = []
+        for i, k in enumerate(("g_ls", "g_sf2", "g_Z", "g_m", "g_LS")):
+            if not ctx.needs_input_grad[i]:
+                outs.append(None)
+                continue
+            shape, dev = ctx.meta[i]
+            outs.append((r[k] * gout.to(r[k].device)).to(dev).reshape(shape))
+        return (*outs, None, None, None)
+
+
 class StochasticVariationalGP(torch.nn.Module):
     """The sparse GP class with the uncollapsed stochastic bound; q(u) = N(m, S) is learnt numerically
     (reference models/svgp.py:24-141): whitened variational strategy, Cholesky variational distribution
@@ -603,8 +633,19 @@ class StochasticVariationalGP(torch.nn.Module):
         self.covar_module = ScaleKernel(RBFKernel(ard_num_dims=train_x.shape[-1]))
         Z = torch.as_tensor(Z_init).detach().clone().to(torch.float64)
         self.inducing_inputs = torch.nn.Parameter(Z[:, None] if Z.dim() == 1 else Z)
-        self.variational_mean = torch.nn.Parameter(torch.zeros(self.num_inducing, dtype=torch.float64))
-        self.chol_variational_covar = torch.nn.Parameter(torch.eye(self.num_inducing, dtype=torch.float64))
+        self.num_classes = None
+        if getattr(likelihood, "name", None) == "multiclass":
+            # C latent GPs with a q(u_c) each (reference models/svgp.py:30-47: MultitaskVariationalStrategy over num_tasks)
+            C = likelihood.num_classes
+            if num_tasks is not None and int(num_tasks) != C:
+                raise ValueError("num_tasks = %r but the likelihood has %d classes" % (num_tasks, C))
+            multiclass_labels(train_y, C)  # ValueError unless the labels are integers 0 .. C-1 and 2 <= C <= 16
+            self.num_classes = C
+            self.variational_mean = torch.nn.Parameter(torch.zeros(C, self.num_inducing, dtype=torch.float64))
+            self.chol_variational_covar = torch.nn.Parameter(torch.eye(self.num_inducing, dtype=torch.float64).repeat(C, 1, 1))
+        else:
+            self.variational_mean = torch.nn.Parameter(torch.zeros(self.num_inducing, dtype=torch.float64))
+            self.chol_variational_covar = torch.nn.Parameter(torch.eye(self.num_inducing, dtype=torch.float64))
         self._engine = engine
         self.to(engine.device if engine is not None else train_x.device)
         # The d + 2 kernel / likelihood hyper-parameters stay on the HOST (the inducing inputs and q(u) live on the device): the
@@ -652,6 +693,9 @@ class StochasticVariationalGP(torch.nn.Module):
         if x_batch.dim() == 1:
             x_batch = x_batch[:, None]
         yb = self._dev(y_batch).reshape(-1)
+        if self.num_classes is not None:
+            return _SVGPMcBoundFn.apply(self.covar_module.base_kernel.lengthscale, self.covar_module.outputscale, self.inducing_inputs,
+                                        self.variational_mean, self.chol_variational_covar, self, self._dev(x_batch), yb)
         if getattr(self.likelihood, "name", "gaussian") in ("bernoulli", "bernoulli_logit"):
             yb = torch.where(yb > 0, torch.ones_like(yb), -torch.ones_like(yb))
         if getattr(self, "batched", True) and hasattr(self._engine_obj(), "svgp_elbo_batch"):
@@ -676,7 +720,7 @@ class StochasticVariationalGP(torch.nn.Module):
                 self.train()
                 self.likelihood.train()
                 optimizer.zero_grad()
-                asyn = getattr(self, "batched", True) and hasattr(self._engine_obj(), "svgp_elbo_batch")
+                asyn = self.num_classes is None and getattr(self, "batched", True) and hasattr(self._engine_obj(), "svgp_elbo_batch")
                 self._async_bounds = asyn  # forward half, copy of the bound + event, reverse half: all enqueued, nothing waited for
                 try:
                     elbo = self.elbo_minibatch(x_batch, y_batch)  # asynchronous: a view of pinned memory, NOT read before the wait
@@ -696,6 +740,8 @@ class StochasticVariationalGP(torch.nn.Module):
     def latent_predictive(self, test_x):
         if test_x.dim() == 1:
             test_x = test_x[:, None]
+        if self.num_classes is not None:
+            return self._mc_predict(test_x, want_probs=False)[:2]
         ls = self.covar_module.base_kernel.lengthscale.detach().reshape(-1).tolist()
         mean, var, info = self._engine_obj().svgp_predict(self._dev(test_x), self._dev(self.inducing_inputs), ls,
                                                           float(self.covar_module.outputscale.detach()),
@@ -705,11 +751,26 @@ class StochasticVariationalGP(torch.nn.Module):
             raise NotPositiveDefiniteError(int(info.to("cpu").item()))
         return mean, var
 
+    def _mc_predict(self, test_x, want_probs):
+        """(mean, var, probs) of the C classes at the test rows, T x C each, from sgp_svgp_mc_predict."""
+        if test_x.dim() == 1:
+            test_x = test_x[:, None]
+        ls = self.covar_module.base_kernel.lengthscale.detach().reshape(-1).tolist()
+        mean, var, probs, info = self._engine_obj().svgp_mc_predict(
+            self._dev(test_x), self._dev(self.inducing_inputs), ls, float(self.covar_module.outputscale.detach()),
+            self._dev(self.variational_mean), self._dev(self.chol_variational_covar), eps=self.likelihood.epsilon, jitter=self.jitter,
+            kernel=self.covar_module.base_kernel.kernel_name, want_probs=want_probs)
+        _raise_on_info(int(info.to("cpu").item()))
+        return mean, var, probs
+
     def posterior_predictive(self, test_x):
         """Predictive through the likelihood (reference models/svgp.py:132-141): a diagonal Gaussian with the
-        noise added, or class-1 probabilities for the Bernoulli likelihood."""
+        noise added, class-1 probabilities for the Bernoulli likelihood, or the T x C class probabilities of the robust-max one."""
         self.eval()
         self.likelihood.eval()
+        if self.num_classes is not None:
+            with torch.no_grad():
+                return self._mc_predict(test_x, want_probs=True)[2]
         with torch.no_grad():
             mean, var = self.latent_predictive(test_x)
             if self._noise_free():

@@ -868,6 +868,30 @@ int sgp_mixture_predict_zs(const double* X, int64_t ldx, const double* y, int64_
 int sgp_svgp_predict(const double* Xs, int64_t ldxs, int64_t T, const double* Z, int64_t ldz, const double* inv_ls,
                      double sf2, double jitter, const double* m, const double* LS, int M, int d, int kernel_id,
                      double* mean, double* var, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+/* ---- multi-class (robust-max) SVGP bound: C latent GPs, one q(u_c) = N(m_c, Ls_c Ls_c^T) per class ----------------------------
+ * [UPSTREAM] GPflow's MultiClass(RobustMax) under SVGP(num_latent_gps = C, whiten = True), as recalled; not checked against it.
+ * The classes share the kernel, Z and the minibatch; with L = chol(sf2 k'(Z, Z) + jitter I), A = L^-1 K_ub, T_c = Ls_c^T A:
+ *   mu_bc = A_b . m_c,  v_bc = sf2 - |A_b|^2 + |T_c,b|^2 (ONE VARIANCE PER CLASS; below 2^-40 sf2 it is raised to that, its derivative 0)
+ *   p_b = sum_i w_i prod_{c != y} Phi((mu_by + sqrt(v_by) x_i - mu_bc) / sqrt(v_bc))      (the 20-point Gauss-Hermite rule)
+ *   ell_b = p_b log(1 - eps) + (1 - p_b) log(eps / (C - 1)),   out[0] = mean_b ell_b - sum_c KL(q(u_c) || N(0, I)) / N_total
+ *   yb: labels 0 .. C-1 as doubles (anything else: NaN for that datum, never an index);  m: C x M;  LS: C x M x M (lower triangles used)
+ *   out (DEVICE, 4) = [out[0] | sum_b ell_b | KL | status word as a double];  info: 1 int, as sgp_svgp_elbo
+ *   with_grads: g_m (C x M), g_LS (C x M x M, lower), g_Z (M x d), g_ls (d), g_sf2 (1) = d out[0] / d .   (DEVICE)
+ * 2 <= C <= SGP_MAX_CLASSES, 0 < eps < 1, sf2 > 0, stationary kernels, the shape limits of sgp_svgp_elbo; anything else is refused
+ * before any launch (SGP_ERR_ARG / _DIM / _WORKSPACE) and the workspace query answers 0.  The number of launches does not depend on C;
+ * every sum runs in a fixed order (bit-reproducible, independent of the workspace's contents).
+ * sgp_svgp_mc_predict: mean, var (C x T; var as formed, no floor) of q(f*_c) at T rows and, when probs != NULL,
+ *   probs[t][c] = (1 - eps) P(c largest) + eps / (C - 1) (1 - P(c largest))  (T x C; the same quadrature, per-class variances, floored)
+ *   workspace: sgp_svgp_mc_workspace_bytes(T, M, d, C).                                                                            */
+size_t sgp_svgp_mc_workspace_bytes(int64_t B, int M, int d, int C);
+int sgp_svgp_mc_elbo(const double* Xb, int64_t ldx, const double* yb, int64_t B, const double* Z, int64_t ldz,
+                     const double* inv_ls, double sf2, double jitter, const double* m, const double* LS, int C, double eps,
+                     int64_t N_total, int M, int d, int kernel_id, int with_grads, double* out,
+                     double* g_m, double* g_LS, double* g_Z, double* g_ls, double* g_sf2,
+                     int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
+int sgp_svgp_mc_predict(const double* Xs, int64_t ldxs, int64_t T, const double* Z, int64_t ldz, const double* inv_ls, double sf2,
+                        double jitter, const double* m, const double* LS, int C, double eps, int M, int d, int kernel_id,
+                        double* mean, double* var, double* probs, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream);
 /* ---- exact GP marginal likelihood (reference models/gpr_hmc.py:43-59: pm.gp.Marginal over sig_f^2 ExpQuad(ls), noise sig_n) ----
  * F = log N(y | 0, A), A = K(X, X) + s2 I (no jitter: WhiteNoise(sig_n) adds s2 to the diagonal and nothing else).
  *   1 <= N <= SGP_MAX_INDUCING, 1 <= d <= SGP_MAX_DIM, kernel_id 0..2 (SGP_KERNEL_COMPOSITE -> SGP_ERR_ARG), sf2 > 0, s2 >= 0;
