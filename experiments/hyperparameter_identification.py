@@ -10,6 +10,10 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
   * three LML surfaces (``ggp_amd.lml_surface``): (sf2, ls) at n = 5 and n = 10 with the noise at 1, and (ls, s2) at n = 30 with sf2 at
     its fitted value -- one launch each.
 
+  * ``--hmc`` (off by default): the Bayesian answer beside every ML-II one -- NUTS over (log ls, log sig_f, log sig_n) on each data set
+    of each cell (``ggp_amd.sample_exact_nuts_batch``: ``--hmc_chains`` chains of ``--hmc_tune`` + ``--hmc_draws`` draws per data set, all
+    chains of a cell in one device-resident batch), recorded as the posterior means per data set.
+
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
 """
@@ -28,10 +32,13 @@ TRUE = {"sig_sd": 5.0, "lengthscale": 2.0, "noise_sd": 1.0}
 AMP_BOUNDS = (1e-5, 1e5)
 
 
-def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed):
+def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None):
     """cells: [(label, n_train, noise variance)].  Fits every cell with the noise fixed at its true variance and with the noise learnt.
-    Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data."""
+    Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data.  ``hmc`` = dict(chains, tune, draws): also
+    res["hmc"] = dict(log_ls, log_sf, log_sn: len(cells) x n_sets posterior means, diverging: the cell's share of diverging draws)."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
+    if hmc:
+        res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
     data = []
     for _, n, var in cells:
         X, Y, latent = ggp_amd.identification_data(n, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
@@ -44,22 +51,32 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r = res[mode]
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["lml"].append(fit.lml), r["n_batches"].append(fit.n_batches)
+        if hmc:
+            post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
+            mean, r = post.posterior_mean(), res["hmc"]
+            r["log_ls"].append(mean[:, 0]), r["log_sf"].append(mean[:, 1]), r["log_sn"].append(mean[:, 2])
+            r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
     return {m: {k: np.array(v) for k, v in r.items()} for m, r in res.items()}, data, latent
 
 
 def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n_sets=100, grid=50, n_noise=30, bimodal=False, seed=57,
-        engine=None):
+        engine=None, hmc=None):
     rng = np.random.default_rng(seed)
     out, summary = {}, {"sizes": list(sizes), "noise_vars": list(noise_vars), "n_sets": n_sets, "true": TRUE}
     t0 = time.time()
-    size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed)
+    size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed, hmc)
     noise_res, noise_data, latent = sweep([(v, n_noise, float(v)) for v in noise_vars], n_sets, 1e4, 5, rng, latent, not bimodal, engine,
-                                          seed)
+                                          seed, hmc)
     summary["fit_seconds"] = time.time() - t0
     for name, res in (("size", size_res), ("noise", noise_res)):
         for mode, r in res.items():
             for k, v in r.items():
                 out["%s_%s_%s" % (name, mode, k)] = v
+            if mode == "hmc":  # the posterior means of the cell's data sets, averaged; beside ML-II's log of the mean fitted lengthscale
+                for k in ("log_ls", "log_sf", "log_sn"):
+                    summary["%s_hmc_mean_%s" % (name, k)] = r[k].mean(1).tolist()
+                summary["%s_hmc_diverging" % name], summary["%s_hmc_seconds" % name] = r["diverging"].tolist(), r["seconds"].tolist()
+                continue
             summary["%s_%s_mean_log_ls" % (name, mode)] = np.log(r["ls"].mean(1)).tolist()
             summary["%s_%s_batched_evaluations" % (name, mode)] = r["n_batches"].tolist()
     # surfaces: (sf2, ls) at the two smallest sizes available, noise at 1; (ls, s2) on the first noise cell with sf2 at its fit
@@ -113,8 +130,13 @@ def main(argv=None, engine=None):
     ap.add_argument("--bimodal", action="store_true", help="inputs around 2 and 8 instead of uniform on the grid")
     ap.add_argument("--seed", type=int, default=57)
     ap.add_argument("--out", default="results")
+    ap.add_argument("--hmc", action="store_true", help="also sample (log ls, log sig_f, log sig_n) of every data set with NUTS")
+    ap.add_argument("--hmc_chains", type=int, default=4)
+    ap.add_argument("--hmc_tune", type=int, default=500)
+    ap.add_argument("--hmc_draws", type=int, default=500)
     args = ap.parse_args(argv)
-    out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine)
+    hmc = {"chains": args.hmc_chains, "tune": args.hmc_tune, "draws": args.hmc_draws} if args.hmc else None
+    out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine, hmc=hmc)
     os.makedirs(args.out, exist_ok=True)
     base = os.path.join(args.out, "hyperparameter_identification")
     np.savez_compressed(base + ".npz", **out)

@@ -38,6 +38,10 @@ _vp, _i64, _i32, _dbl, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_siz
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 
+_EN_BEGIN = [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+_EN_ADVANCE = [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]
+EXACT_NUTS_BAD_START = 1  # SGP_EXACT_NUTS_BAD_START
+
 # name -> (restype, argtypes) ; mirrors include/sgp.h line by line
 PROTOTYPES = {
     "sgp_abi_version": (_i32, []),
@@ -239,7 +243,20 @@ PROTOTYPES = {
                            _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# the companion library libsgp_exact_nuts_hip.so (include/sgp_exact_nuts.h): C device-resident NUTS chains over the exact marginal
+# likelihood, one workgroup each (begin, then advance until all have finished)
+EXACT_NUTS_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_exact_nuts_hip.so")
+EXACT_NUTS_PROTOTYPES = {
+    "sgp_exact_nuts_batch_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "sgp_exact_nuts_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_exact_nuts_batch_begin": (_i32, _EN_BEGIN),
+    "sgp_ctx_exact_nuts_batch_begin": (_i32, [_vp] + _EN_BEGIN),
+    "sgp_exact_nuts_batch_advance": (_i32, _EN_ADVANCE),
+    "sgp_ctx_exact_nuts_batch_advance": (_i32, [_vp] + _EN_ADVANCE),
+}
+
 _LIB = None
+_EXACT_NUTS_LIB = None
 
 
 def load_library(path: str | None = None):
@@ -268,6 +285,29 @@ def load_library(path: str | None = None):
     if path is None:
         _LIB = lib
     return lib
+
+
+def load_exact_nuts_library():
+    """dlopen the companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
+    global _EXACT_NUTS_LIB
+    if _EXACT_NUTS_LIB is None:
+        load_library()
+        p = EXACT_NUTS_LIB_PATH
+        if not os.path.exists(p):
+            raise SgpLibraryError("%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % p)
+        try:
+            lib = C.CDLL(p)
+        except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+            raise SgpLibraryError("cannot load %s: %s" % (p, e)) from e
+        for name, (res, args) in EXACT_NUTS_PROTOTYPES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise SgpLibraryError("%s does not export %s" % (p, name)) from e
+            fn.restype = res
+            fn.argtypes = args
+        _EXACT_NUTS_LIB = lib
+    return _EXACT_NUTS_LIB
 
 
 def check(fn_name: str, status: int):

@@ -17,6 +17,9 @@ LIB_NAME = "libsgp_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ["sgp_ctx.hip", "sgp_suffstats_fwd.hip", "sgp_suffstats_i8.hip", "sgp_suffstats_bwd.hip", "sgp_suffstats_bwd_lo.hip", "sgp_dense.hip", "sgp_tail.hip", "sgp_sgpmc.hip", "sgp_sgpmc_lik.hip", "sgp_sgpmc_mc.hip", "sgp_sgpmc_comp.hip", "sgp_svgp.hip", "sgp_svgp_mc.hip", "sgp_composite.hip", "sgp_small.hip", "sgp_exact.hip", "sgp_exact_batch.hip"]
 VERSION_SCRIPT = "libsgp.map"
+# Companion libraries: (library, sources, public header).  Each is one more shared object beside libsgp_hip.so with a C header of its
+# own, linked to the core library; the core's surface (include/sgp.h) does not grow with them.
+COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h")]
 PUBLIC_HEADER = os.path.join("..", "..", "include", "sgp.h")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # only the SGP_API symbols of include/sgp.h leave the library
 
@@ -45,8 +48,57 @@ def _digest() -> str:
     return h.hexdigest()
 
 
+def _companion_digest(core_digest: str, sources, header) -> str:
+    """The core library's digest (flags, every csrc header, the version script) plus the companion's own sources and public header."""
+    h = hashlib.sha256(core_digest.encode())
+    for f in list(sources) + [os.path.join("..", "..", "include", header)]:
+        h.update(os.path.basename(f).encode())
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def build_companions(force: bool = False, verbose: bool = False):
+    """Compile and link every companion library (after the core library, which they link to).  Returns their paths."""
+    hipcc, core, paths = None, _digest(), []
+    for name, sources, header in COMPANIONS:
+        path = os.path.join(CSRC, name)
+        stamp, digest = path + ".sha256", _companion_digest(core, sources, header)
+        paths.append(path)
+        if not force and os.path.exists(path) and os.path.exists(stamp):
+            with open(stamp) as fh:
+                if fh.read().strip() == digest:
+                    continue
+        hipcc = hipcc or _hipcc()
+        objs = []
+        for src in sources:
+            obj = os.path.join(CSRC, src.replace(".hip", ".o"))
+            cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd += os.environ.get("SGP_EXTRA_HIPCC_FLAGS", "").split()
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("hipcc failed on %s:\n%s" % (src, r.stdout))
+            objs.append(obj)
+        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, VERSION_SCRIPT),
+               "-Wl,-rpath,$ORIGIN", "-o", path] + objs + ["-L" + CSRC, "-l:" + LIB_NAME]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link of %s failed:\n%s" % (name, r.stdout))
+        with open(stamp, "w") as fh:
+            fh.write(digest)
+    return paths
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile every HIP translation unit for gfx950 and link them into csrc/libsgp_hip.so."""
+    """Compile every HIP translation unit for gfx950 and link them into csrc/libsgp_hip.so, then the companion libraries."""
+    _build_core(force, verbose)
+    build_companions(force, verbose)
+    return LIB_PATH
+
+
+def _build_core(force: bool = False, verbose: bool = False) -> str:
     stamp = LIB_PATH + ".sha256"
     digest = _digest()
     if not force and os.path.exists(LIB_PATH) and os.path.exists(stamp):

@@ -1,48 +1,11 @@
 // P independent exact-GP marginal likelihoods in ONE launch (LML surfaces, multi-start ML-II): one 256-thread workgroup per problem, the
-// whole problem in that workgroup's LDS.  No inter-workgroup communication, no flags, no spins, no atomics: a workgroup reads its
-// data set and its row of theta, and writes its own rows of out / grads / info.
-//
-//   A = sf2 k'(X, X) + s2 I ; L = chol(A) ; u = L^-1 y ; F = -1/2 u.u - sum log L_ii - N/2 log 2 pi            (value-only stops here)
-//   L^-1 in place ; alpha = L^-T u ; tr A^-1 = |L^-1|_F^2 ; G = alpha alpha^T - L^-T L^-1 (16 x 16 tiles, never stored)
-//   dF/dls_q = 1/2 sum G dA/dls_q ; dF/dsf2 = 1/2 sum G k' ; dF/ds2 = 1/2 (alpha.alpha - tr A^-1)              (sgp_exact_eval's convention)
-//
-// The LDS image M is Nr x Nr (Nr = N rounded up to 16, identity in the padding) inside NP x (NP + 2) doubles, NP in {32, 64, 128} the
-// size class.  Row stride NP + 2 = 2 (mod 32) eight-byte slots:
-//   * "16 rows x 4 consecutive columns" (MFMA operands whose contraction index runs along a row: the rank-16 trailing update, the Inv
-//     operand of the triangular inversion) -- a 32-lane group touches slots 2 r + c, r < 16, c < 2: all distinct;
-//   * "4 rows x 16 consecutive columns" (contraction index running down a column: the A^-1 tiles, the dominant N^3 / 3 phase) -- the
-//     four lane groups of an MFMA take the rows k0 + {0, 8, 4, 12} + s instead of k0 + 4 s + {0, 1, 2, 3}, so the two rows of a
-//     32-lane group are 8 apart = 16 slots: all distinct.  (Any fixed assignment of the 16 rows to the 16 (group, step) pairs is the
-//     same sum in another, still fixed, order.)
-//   * row reads (assembly, alpha) are contiguous; the thread-per-row panel solves and the accumulator-tile loads and stores (two
-//     adjacent rows per lane group) are 2-way -- 32 eight-byte accesses per thread and panel, off the MFMA phases.
-// Every sum has a fixed order and depends on nothing outside the problem: the same bits on every call, stream and batch.
-#include "sgp_common.hpp"
+// whole problem in that workgroup's LDS (sgp_exact_batch.hpp: eb_load + eb_eval, shared with the batched NUTS of sgp_exact_nuts.hip).  No
+// inter-workgroup communication, no flags, no spins, no atomics: a workgroup reads its data set and its row of theta, and writes its own
+// rows of out / grads / info.  Every sum has a fixed order and depends on nothing outside the problem: the same bits on every call,
+// stream and batch.
+#include "sgp_exact_batch.hpp"
 
 namespace sgp {
-
-constexpr int EB_MAXN = 128;
-constexpr int EB_MAXD = 8;
-constexpr int64_t EB_MAXP = (1 << 24) - 1;  // one workgroup per problem: P x 256 work-items stay below the 2^32 of one launch
-constexpr int EB_XLD = EB_MAXD + 1;  // odd stride: x_j reads of the epilogue (16 consecutive rows) hit distinct banks
-
-template <int NP>
-struct EbShared {
-  double M[NP][NP + 2];
-  double x[NP][EB_XLD];        // the data set's rows (unscaled: differences are formed first, then scaled)
-  double yv[NP];               // y, then u = L^-1 y
-  double al[NP];               // alpha
-  double red[4][EB_MAXD + 2];  // block_sum256's four words / the waves' gradient partials
-  int bad;
-};
-
-// (row, column) of entry t of a lower triangle stored row by row: t = r (r + 1) / 2 + c, c <= r
-__device__ __forceinline__ void eb_tri(int t, int& r, int& c) {
-  r = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-  while ((r + 1) * (r + 2) / 2 <= t) ++r;
-  while (r * (r + 1) / 2 > t) --r;
-  c = t - r * (r + 1) / 2;
-}
 
 template <int KID, int NP>
 __global__ __launch_bounds__(256) void exact_batch_kernel(const double* __restrict__ X, int64_t x_stride, int64_t ldx,
@@ -52,305 +15,10 @@ __global__ __launch_bounds__(256) void exact_batch_kernel(const double* __restri
                                                           int* __restrict__ info) {
   __shared__ EbShared<NP> sh;
   const int64_t p = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, l4 = lane >> 4;
-  const int Nr = round_up(N, 16), nb = Nr / 16;
-  const double* th = theta + p * (d + 2);
-  const double sf2 = th[d], s2 = th[d + 1];
   const double* Xp = X + (int64_t)(ix ? ix[p] : 0) * x_stride;
   const double* Yp = Y + (int64_t)(iy ? iy[p] : 0) * y_stride;
-  double ils[EB_MAXD];
-#pragma unroll
-  for (int q = 0; q < EB_MAXD; ++q) ils[q] = q < d ? 1.0 / th[q] : 0.0;
-  if (tid == 0) {  // a hyper-parameter that is not a positive finite number (NaN included) is reported as pivot 1: 1 / ls loses a sign
-    bool pos = true;
-    for (int q = 0; q < d + 2; ++q) pos = pos && th[q] > 0.0 && th[q] < __builtin_inf();
-    sh.bad = pos ? 0 : 1;
-  }
-  for (int e = tid; e < Nr * d; e += 256) {
-    const int i = e / d, q = e - i * d;
-    sh.x[i][q] = i < N ? Xp[(int64_t)i * ldx + q] : 0.0;
-  }
-  for (int i = tid; i < Nr; i += 256) sh.yv[i] = i < N ? Yp[i] : 0.0;
-  __syncthreads();
-
-  // ---- A: lower triangle, zero above it, identity in the padding ----
-  for (int e = tid; e < Nr * Nr; e += 256) {
-    const int i = e / Nr, j = e - i * Nr;
-    double v = 0.0;
-    if (i < N && j <= i) {
-      double r2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < EB_MAXD; ++q) {
-        if (q < d) {
-          const double df = (sh.x[i][q] - sh.x[j][q]) * ils[q];
-          r2 = fma(df, df, r2);
-        }
-      }
-      v = sf2 * kprofile<KID>(r2);
-      if (i == j) v += s2;
-    } else if (i == j) {
-      v = 1.0;
-    }
-    sh.M[i][j] = v;
-  }
-  __syncthreads();
-
-  // ---- Cholesky, right-looking by 16-column panels, with the forward substitution of y carried along ----
-  // A pivot at or below 8 N 2^-53 times the diagonal of A (sf2 + s2 in every row) is rounding noise of the updates that formed it: A is
-  // not numerically positive definite.  The first such pivot is reported (1-based); the factorization continues on a unit pivot.
-  const double gate = (sf2 + s2) * (8.0 * (double)N) * 0x1p-53;
-  for (int pb = 0; pb < nb; ++pb) {
-    const int c0 = 16 * pb;
-    if (wave == 0) {  // (a) the 16 x 16 diagonal block: lane <-> row (the four lane groups hold copies), columns exchanged by shuffles
-      double a[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) a[k] = sh.M[c0 + l15][c0 + k];
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        double dj = __shfl(a[jj], jj, 64);
-        if (c0 + jj < N && !(dj > gate)) {  // (NaN included)
-          if (lane == 0 && sh.bad == 0) sh.bad = c0 + jj + 1;
-          dj = 1.0;
-        }
-        const double piv = sqrt(dj);
-        const double l = (l15 == jj) ? piv : a[jj] / piv;
-        a[jj] = l;
-#pragma unroll
-        for (int k = jj + 1; k < 16; ++k) a[k] = fma(-l, __shfl(l, k, 64), a[k]);
-      }
-      if (lane < 16) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sh.M[c0 + l15][c0 + k] = (k <= l15) ? a[k] : 0.0;
-      }
-    }
-    __syncthreads();
-    const int nbelow = Nr - c0 - 16;
-    if (tid < nbelow) {  // (b) the rows below: thread <-> row, x = row D^-T by substitution (the block's entries are broadcast reads)
-      const int i = c0 + 16 + tid;
-      double x[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) x[k] = sh.M[i][c0 + k];
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        double s = x[jj];
-#pragma unroll
-        for (int k = 0; k < jj; ++k) s = fma(-x[k], sh.M[c0 + jj][c0 + k], s);
-        x[jj] = s / sh.M[c0 + jj][c0 + jj];
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sh.M[i][c0 + k] = x[k];
-    }
-    if (wave == 3) {  // ... and the block's 16 entries of u = L^-1 y
-      double lrow[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) lrow[k] = sh.M[c0 + l15][c0 + k];
-      double v = sh.yv[c0 + l15];
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        const double xj = __shfl(v, jj, 64) / __shfl(lrow[jj], jj, 64);
-        v = (l15 == jj) ? xj : (l15 > jj ? fma(-lrow[jj], xj, v) : v);
-      }
-      if (lane < 16) sh.yv[c0 + l15] = v;
-    }
-    __syncthreads();
-    {  // (c) rank-16 update of the trailing lower-triangle tiles on the matrix cores; wave <-> tiles wave, wave + 4, ...
-      const int m = nb - pb - 1;
-      for (int t = wave; t < m * (m + 1) / 2; t += 4) {
-        int ri, rj;
-        eb_tri(t, ri, rj);
-        const int i0 = 16 * (pb + 1 + ri), j0 = 16 * (pb + 1 + rj);
-        d4 acc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = sh.M[i0 + l4 + 4 * r][j0 + l15];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = mfma16(-sh.M[i0 + l15][c0 + 4 * s + l4], sh.M[j0 + l15][c0 + 4 * s + l4], acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sh.M[i0 + l4 + 4 * r][j0 + l15] = acc[r];
-      }
-      if (tid < nbelow) {  // y below the block
-        const int i = c0 + 16 + tid;
-        double s = sh.yv[i];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s = fma(-sh.M[i][c0 + k], sh.yv[c0 + k], s);
-        sh.yv[i] = s;
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- the scalars of the value: one entry per thread, block_sum256's fixed tree ----
-  double uu = 0.0, ld = 0.0;
-  if (tid < N) {
-    uu = sh.yv[tid] * sh.yv[tid];
-    ld = log(sh.M[tid][tid]);
-  }
-  uu = block_sum256(uu, &sh.red[0][0]);
-  ld = block_sum256(ld, &sh.red[0][0]);
-  const int bad = sh.bad;
-  const double nan = __builtin_nan("");
-  const double F = -0.5 * uu - ld - 0.5 * (double)N * 1.8378770664093453;  // log 2 pi
-  if (bad != 0 || !with_grad) {
-    if (tid == 0) {
-      out[p * 4 + 0] = bad ? nan : F;
-      out[p * 4 + 1] = bad ? nan : uu;
-      out[p * 4 + 2] = bad ? nan : 2.0 * ld;
-      out[p * 4 + 3] = nan;
-      info[p] = bad;
-    }
-    if (with_grad && tid < d + 2) grads[p * (d + 2) + tid] = nan;
-    return;
-  }
-
-  // ---- L^-1 in place, block column by block column from the right:  Inv[below][J] = -Inv[below][below] L[below][J] Inv[J][J] ----
-  for (int J = nb - 1; J >= 0; --J) {
-    const int c0 = 16 * J, m = nb - 1 - J;
-    d4 T[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {  // T = Inv[below][below] L[below][J]: every tile into registers before the panel is overwritten
-      T[u] = d4{0.0, 0.0, 0.0, 0.0};
-      const int ri = wave + 4 * u;
-      if (ri < m) {
-        const int i0 = 16 * (J + 1 + ri);
-        for (int k0 = c0 + 16; k0 <= i0; k0 += 16) {
-#pragma unroll
-          for (int s = 0; s < 4; ++s) T[u] = mfma16(sh.M[i0 + l15][k0 + 4 * s + l4], sh.M[k0 + 4 * s + l4][c0 + l15], T[u]);
-        }
-      }
-    }
-    double xinv[16];  // wave 3, lane c < 16: column c of the inverse of the diagonal block (zero above the diagonal)
-    if (wave == 3) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        double s = (r == l15) ? 1.0 : 0.0;
-#pragma unroll
-        for (int q = 0; q < r; ++q) s = fma(-sh.M[c0 + r][c0 + q], xinv[q], s);
-        xinv[r] = s / sh.M[c0 + r][c0 + r];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int ri = wave + 4 * u;
-      if (ri < m) {
-        const int i0 = 16 * (J + 1 + ri);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sh.M[i0 + l4 + 4 * r][c0 + l15] = T[u][r];
-      }
-    }
-    if (wave == 3 && lane < 16) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sh.M[c0 + r][c0 + l15] = xinv[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {  // tile <- -T Inv[J][J]: a wave reads its own tile whole, then overwrites it
-      const int ri = wave + 4 * u;
-      if (ri < m) {
-        const int i0 = 16 * (J + 1 + ri);
-        double a[4], b[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          a[s] = -sh.M[i0 + l15][c0 + 4 * s + l4];
-          b[s] = sh.M[c0 + 4 * s + l4][c0 + l15];
-        }
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = mfma16(a[s], b[s], acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sh.M[i0 + l4 + 4 * r][c0 + l15] = acc[r];
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- alpha = L^-T u, tr A^-1 = |L^-1|_F^2 : thread <-> column ----
-  double tr = 0.0, aa = 0.0;
-  if (tid < Nr) {
-    double s = 0.0, t = 0.0;
-    for (int k = tid; k < Nr; ++k) {
-      const double v = sh.M[k][tid];
-      s = fma(v, sh.yv[k], s);
-      t = fma(v, v, t);
-    }
-    sh.al[tid] = tid < N ? s : 0.0;
-    if (tid < N) {
-      tr = t;
-      aa = s * s;
-    }
-  }
-  tr = block_sum256(tr, &sh.red[0][0]);
-  aa = block_sum256(aa, &sh.red[0][0]);
-  __syncthreads();  // red is reused below
-
-  // ---- the lower-triangle 16 x 16 tiles of A^-1 = L^-T L^-1 on the matrix cores, each folded into the d + 1 sums at once ----
-  double sq[EB_MAXD];
-#pragma unroll
-  for (int q = 0; q < EB_MAXD; ++q) sq[q] = 0.0;
-  double sk = 0.0;
-  const int kperm = 8 * (l4 & 1) + 4 * (l4 >> 1);  // see the head of the file
-  for (int t = wave; t < nb * (nb + 1) / 2; t += 4) {
-    int bi, bj;
-    eb_tri(t, bi, bj);
-    const int i0 = 16 * bi, j0 = 16 * bj;
-    d4 acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = i0; k0 < Nr; k0 += 16) {  // (A^-1)_ij = sum_{k >= max(i, j)} (L^-1)_ki (L^-1)_kj : the zeros above are never multiplied
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const double* row = &sh.M[k0 + kperm + s][0];
-        acc = mfma16(row[i0 + l15], row[j0 + l15], acc);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {  // element r of the accumulator: row (lane >> 4) + 4 r, column lane & 15
-      const int li = l4 + 4 * r, gi = i0 + li, gj = j0 + l15;
-      double w = (bi == bj) ? (li > l15 ? 2.0 : (li == l15 ? 1.0 : 0.0)) : 2.0;
-      if (gi >= N || gj >= N) w = 0.0;
-      const double g = w * fma(sh.al[gi], sh.al[gj], -acc[r]);
-      double r2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < EB_MAXD; ++q) {
-        if (q < d) {
-          const double df = (sh.x[gi][q] - sh.x[gj][q]) * ils[q];
-          r2 = fma(df, df, r2);
-        }
-      }
-      double kp, hp;
-      kprofile_grad<KID>(r2, kp, hp);
-      sk = fma(g, kp, sk);
-      const double e = g * hp;
-#pragma unroll
-      for (int q = 0; q < EB_MAXD; ++q) {
-        if (q < d) {
-          const double df = (sh.x[gi][q] - sh.x[gj][q]) * ils[q];
-          sq[q] = fma(e * df, df, sq[q]);
-        }
-      }
-    }
-  }
-  sk = wave_sum(sk);
-  if (lane == 0) sh.red[wave][d] = sk;
-#pragma unroll
-  for (int q = 0; q < EB_MAXD; ++q) {
-    if (q < d) {
-      const double a = wave_sum(sq[q]);
-      if (lane == 0) sh.red[wave][q] = a;
-    }
-  }
-  __syncthreads();
-  if (tid <= d) {
-    const double s = (sh.red[0][tid] + sh.red[1][tid]) + (sh.red[2][tid] + sh.red[3][tid]);
-    grads[p * (d + 2) + tid] = tid == d ? 0.5 * s : -sf2 * (1.0 / th[tid]) * s;
-  }
-  if (tid == 0) {
-    grads[p * (d + 2) + d + 1] = 0.5 * (aa - tr);
-    out[p * 4 + 0] = F;
-    out[p * 4 + 1] = uu;
-    out[p * 4 + 2] = 2.0 * ld;
-    out[p * 4 + 3] = tr;
-    info[p] = 0;
-  }
+  eb_load<NP>(sh, sh.yv, Xp, ldx, Yp, N, d);
+  eb_eval<KID, NP>(sh, theta + p * (d + 2), N, d, with_grad, out + p * 4, grads + p * (d + 2), info + p);
 }
 
 template <int KID>
@@ -394,7 +62,7 @@ extern "C" size_t sgp_exact_batch_workspace_bytes(int64_t P, int N, int d, int w
 extern "C" int sgp_exact_batch_occupancy(int N, int kernel_id) {
   const int chk = exact_batch_check(1, N, 1, kernel_id);
   if (chk != SGP_OK) return chk;
-  const int NP = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
+  const int NP = eb_size_class(N);
   switch (kernel_id) {
     case SGP_KERNEL_RBF: return occupancy_eb<SGP_KERNEL_RBF>(NP);
     case SGP_KERNEL_MATERN32: return occupancy_eb<SGP_KERNEL_MATERN32>(NP);
@@ -410,7 +78,7 @@ extern "C" int sgp_exact_eval_batch(const double* X, int64_t x_stride, int64_t l
   if (!X || !Y || !theta || !out || !info || (with_grad && !grads) || ldx < d || x_stride < 0 || y_stride < 0) return SGP_ERR_ARG;
   if (!ws || ws_bytes < sgp_exact_batch_workspace_bytes(P, N, d, with_grad)) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int NP = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
+  const int NP = eb_size_class(N);
   const int wg = with_grad ? 1 : 0;
   switch (kernel_id) {
     case SGP_KERNEL_RBF: launch_eb<SGP_KERNEL_RBF>(NP, P, st, X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, wg, out, grads, info); break;

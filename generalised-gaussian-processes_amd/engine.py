@@ -1000,6 +1000,68 @@ class HipEngine:
         _lib.check("sgp_exact_eval_batch", st)
         return out[:, 0], out, grads, info
 
+    # Evaluations one resident workgroup runs back to back in a launch of ``exact_nuts_batch`` by default (1024 x the
+    # measured 138 us per evaluation of one chain at N = 128 keeps the longest launch near 0.14 s); shared among the waves of workgroups
+    # when there are more chains than the chip holds at a time.
+    EXACT_NUTS_LAUNCH_EVALS = 1024
+
+    @property
+    def exact_nuts_lib(self):
+        """The companion library of the batched sampler (include/sgp_exact_nuts.h), loaded on first use."""
+        return _lib.load_exact_nuts_library()
+
+    def exact_nuts_evals_per_launch(self, C: int, N: int, kernel="rbf") -> int:
+        """The default ``evals_per_launch`` of ``exact_nuts_batch``: ``EXACT_NUTS_LAUNCH_EVALS`` divided by the number of waves of
+        workgroups C chains make on this device (chains per CU from ``sgp_exact_nuts_batch_occupancy``)."""
+        per_cu = int(self.exact_nuts_lib.sgp_exact_nuts_batch_occupancy(int(N), _kernel_id(kernel)))
+        _lib.check("sgp_exact_nuts_batch_occupancy", min(per_cu, 0))
+        slots = max(1, per_cu * torch.cuda.get_device_properties(self.device).multi_processor_count)
+        return max(1, self.EXACT_NUTS_LAUNCH_EVALS // -(-int(C) // slots))
+
+    def exact_nuts_batch(self, X, Y, q0, seeds, n_tune, n_draws, ix=None, iy=None, kernel="rbf", jitter=0.0, max_treedepth=10,
+                         step_scale=0.25, target_accept=0.8, evals_per_launch=None):
+        """C independent NUTS chains over the exact marginal likelihood, one workgroup each, entirely on the device (include/sgp_exact_nuts.h:
+        sgp_exact_nuts_batch_begin / _advance).  X: nX x N x d (or N x d), Y: nY x N (or N) -- device tensors; chain c samples data set
+        ix[c] with target iy[c] (None: set 0) from q0[c] (C x (d + 2), unconstrained) with the splitmix64 stream of seeds[c].  The run is
+        a loop of bounded launches (``evals_per_launch`` evaluations per chain each, default ``exact_nuts_evals_per_launch``) with one
+        8-byte read-back per launch; no output but ``seconds`` depends on how it is cut.  Returns host tensors: samples [C, n_draws,
+        d + 2], stats [C, n_draws, 8], seconds [C, n_draws], evaluations [C], draws [C] (int64), info [C] (int32: 0, or
+        ``_lib.EXACT_NUTS_BAD_START`` -- no finite density at the start, that chain's rows are NaN), and ``launches``."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        nX, N, d = X.shape
+        nY = Y.shape[0]
+        self._chk(X, "X"), self._chk(Y, "Y")
+        q0 = torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)).reshape(-1, d + 2)
+        q0 = q0.to(self.device).contiguous()
+        C_ = q0.shape[0]
+        seeds = np.asarray([int(s) & ((1 << 64) - 1) for s in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)], dtype=np.uint64)
+        if Y.shape[1] != N or seeds.size != C_ or n_draws < 1 or n_tune < 0:
+            raise ValueError("shapes: X %s, Y %s, q0 %s, %d seeds, n_tune %d, n_draws %d" % (tuple(X.shape), tuple(Y.shape), tuple(q0.shape),
+                                                                                            seeds.size, n_tune, n_draws))
+        seeds_d = torch.as_tensor(seeds.view(np.int64)).to(self.device)
+        ix, iy = self._set_index(ix, nX, C_, "ix"), self._set_index(iy, nY, C_, "iy")
+        kid = _kernel_id(kernel)
+        samples, stats, seconds = self.empty(C_, n_draws, d + 2), self.empty(C_, n_draws, 8), self.empty(C_, n_draws)
+        counts = torch.empty(2, C_, dtype=torch.int64, device=self.device)
+        info = torch.empty(C_, dtype=torch.int32, device=self.device)
+        ws = self._workspace("exact_nuts", self.exact_nuts_lib.sgp_exact_nuts_batch_workspace_bytes(C_, N, d))
+        outs = (self._ptr(samples), self._ptr(stats), self._ptr(seconds), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(info))
+        _lib.check("sgp_exact_nuts_batch_begin", self.exact_nuts_lib.sgp_ctx_exact_nuts_batch_begin(
+            self._c(), self._ptr(q0), self._ptr(seeds_d), C_, N, d, kid, int(n_tune), int(n_draws), int(max_treedepth), float(step_scale),
+            float(target_accept), *outs, self._ptr(ws), ws.numel(), self._stream()))
+        if evals_per_launch is None:
+            evals_per_launch = self.exact_nuts_evals_per_launch(C_, N, kernel)
+        finished, launches = C.c_int64(0), 0
+        while finished.value < C_:
+            _lib.check("sgp_exact_nuts_batch_advance", self.exact_nuts_lib.sgp_ctx_exact_nuts_batch_advance(
+                self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), C_, N, d, kid, float(jitter), *outs,
+                int(evals_per_launch), C.byref(finished), self._ptr(ws), ws.numel(), self._stream()))
+            launches += 1
+        counts = counts.to("cpu")
+        return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
+                "draws": counts[1], "info": info.to("cpu"), "launches": launches}
+
     def exact_predict(self, Xs, X, ls, sf2, s2, factors, kernel="rbf", pred_noise=True, full_cov=False):
         """Exact posterior predictive at the rows of Xs from ``exact_eval(..., want_factors=True)``'s factors at the same (X, theta)
         (include/sgp.h: sgp_exact_predict).  Returns (mean, var, cov or None) as device tensors; nothing is synchronised."""

@@ -23,7 +23,9 @@ import torch
 from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, few_host_threads
 from .gp_shim import (ExactGP, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, LazyPredictive,
                       MultivariateNormal, RBFKernel, ScaleKernel, TrainPrior, ZeroMean)
+from .exact_nuts import sample_exact_nuts_batch
 from .hmc import Trace, next_seed, sample_nuts, sample_nuts_device, trace_summary
+from .ml2 import MAX_D as EXACT_NUTS_MAX_D, MAX_N as EXACT_NUTS_MAX_N
 from .targets import EXACT_MAX_N, ExactHmcTarget, HmcTarget, JointHmcTarget, multiclass_labels
 
 FULL_COV_MAX_T = 4096  # predictive covariance is T x T; beyond this only mean / variance are formed
@@ -387,9 +389,14 @@ class GPR_HMC(ExactGP):  # noqa: N801  (reference class name)
     """Exact GP regression with (ls, sig_f, sig_n) sampled by NUTS on the exact marginal likelihood (reference models/gpr_hmc.py:23-81):
     the yardstick that shows what sparsity costs.  Priors as ``BayesianSparseGPR_HMC``; covariance sig_f^2 ExpQuad(ls), noise sig_n,
     no jitter (``ExactHmcTarget``).  N <= 4096 training rows.  ``model(x)`` follows ExactGP: the prior in training mode, the exact
-    posterior at the bound hyper-parameters in eval mode (full covariance); ``likelihood(model(x))`` adds the noise."""
+    posterior at the bound hyper-parameters in eval mode (full covariance); ``likelihood(model(x))`` adds the noise.
 
-    def __init__(self, train_x, train_y, likelihood, engine=None, seed: Optional[int] = None):
+    ``device_sampler=True`` (opt-in): where N <= 128 and d <= 8 the chain runs entirely on the device, one workgroup evaluating and
+    sampling (``sample_exact_nuts_batch``, one chain); beyond that size, and by default, nothing changes: the host-driven sampler over
+    ``sgp_exact_eval``.  The reference's own GPR_HMC workloads (Boston, N ~ 455, and larger) are beyond N = 128 and stay on that path;
+    the device sampler serves the small-N identification study, where one workgroup per chain lets hundreds of chains share a launch."""
+
+    def __init__(self, train_x, train_y, likelihood, engine=None, seed: Optional[int] = None, device_sampler: bool = False):
         super().__init__(train_x, train_y, likelihood)
         if train_x.dim() == 1:
             train_x = train_x[:, None]
@@ -404,6 +411,7 @@ class GPR_HMC(ExactGP):  # noqa: N801  (reference class name)
         self.covar_module = ScaleKernel(RBFKernel(ard_num_dims=self.data_dim))
         self._engine = engine
         self._seed = seed
+        self.device_sampler = bool(device_sampler)
         self._n_hmc_calls = 0
         self._target: Optional[ExactHmcTarget] = None
         dev = engine.device if engine is not None else train_x.device
@@ -457,7 +465,14 @@ class GPR_HMC(ExactGP):  # noqa: N801  (reference class name)
         """``pm.sample(n_samples, tune=tune, chains=1)`` over the exact model; the trace has ``ls``, ``sig_f``, ``sig_n``."""
         if int(input_dim) != self.data_dim:
             raise ValueError("input_dim %d does not match the training inputs (%d)" % (input_dim, self.data_dim))
-        return sample_nuts(self._exact_target(), n_samples, tune, seed=next_seed(self))
+        t = self._exact_target()
+        if self.device_sampler and t.X.shape[0] <= EXACT_NUTS_MAX_N and t.d <= EXACT_NUTS_MAX_D and hasattr(t.engine, "exact_nuts_batch"):
+            r = sample_exact_nuts_batch(t.X, t.y, n_samples, tune, chains=1, kernel=t.kernel, seed=next_seed(self), jitter=t.jitter,
+                                        engine=t.engine)
+            if int(r.info[0, 0]) != 0:
+                raise RuntimeError("could not find a starting point with finite log-density")
+            return r.traces[0][0]
+        return sample_nuts(t, n_samples, tune, seed=next_seed(self))
 
     def train_model(self):
         """50 tuning + 10 draws (reference models/gpr_hmc.py:63-79).  Returns (trace_hyper, [step_size], [perf_time sum])."""
