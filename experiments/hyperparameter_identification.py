@@ -12,7 +12,11 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
 
   * ``--hmc`` (off by default): the Bayesian answer beside every ML-II one -- NUTS over (log ls, log sig_f, log sig_n) on each data set
     of each cell (``ggp_amd.sample_exact_nuts_batch``: ``--hmc_chains`` chains of ``--hmc_tune`` + ``--hmc_draws`` draws per data set, all
-    chains of a cell in one device-resident batch), recorded as the posterior means per data set.
+    chains of a cell in one device-resident batch), recorded as the posterior means per data set;
+  * ``--holdout K`` (0 by default): K more points per data set, kept out of the fit and the sampling: the held-out NLPD and RMSE of the
+    ML-II plug-in (``Ml2Result.predict``) and, with ``--hmc``, of the mixture over the draws (``ExactNutsResult.predict``) -- whether
+    sampling theta predicts better than plugging in its ML-II value (summary keys ``<sweep>_ml2_nlpd``, ``_hmc_nlpd``, ``_ml2_rmse``,
+    ``_hmc_rmse``, one entry per cell).
 
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
@@ -32,17 +36,23 @@ TRUE = {"sig_sd": 5.0, "lengthscale": 2.0, "noise_sd": 1.0}
 AMP_BOUNDS = (1e-5, 1e5)
 
 
-def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None):
+def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None, holdout=0):
     """cells: [(label, n_train, noise variance)].  Fits every cell with the noise fixed at its true variance and with the noise learnt.
     Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data.  ``hmc`` = dict(chains, tune, draws): also
-    res["hmc"] = dict(log_ls, log_sf, log_sn: len(cells) x n_sets posterior means, diverging: the cell's share of diverging draws)."""
+    res["hmc"] = dict(log_ls, log_sf, log_sn: len(cells) x n_sets posterior means, diverging: the cell's share of diverging draws).
+    ``holdout`` = K > 0: K more points are drawn per cell and kept out of the fit and the sampling; res["learn"] (the ML-II plug-in,
+    ``Ml2Result.predict``) and res["hmc"] (the mixture over the draws, ``ExactNutsResult.predict``) gain nlpd, rmse: len(cells) x n_sets."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
     if hmc:
         res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
+    if holdout:
+        for m in ("learn", "hmc") if hmc else ("learn",):
+            res[m].update(nlpd=[], rmse=[])
     data = []
     for _, n, var in cells:
-        X, Y, latent = ggp_amd.identification_data(n, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
+        X, Y, latent = ggp_amd.identification_data(n + holdout, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
             k: TRUE[k] for k in ("sig_sd", "lengthscale")})
+        X, Y, X_test, Y_test = X[:n], Y[:, :n], X[n:], Y[:, n:]  # (the points are a random choice of the grid: any K of them are)
         data.append((X, Y))
         bounds = np.array([(1e-2, ls_upper), AMP_BOUNDS, AMP_BOUNDS])
         for mode in ("fixed", "learn"):
@@ -51,27 +61,37 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r = res[mode]
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["lml"].append(fit.lml), r["n_batches"].append(fit.n_batches)
+            if holdout and mode == "learn":
+                pred = fit.predict(X_test, Y_test)
+                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
         if hmc:
             post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
             mean, r = post.posterior_mean(), res["hmc"]
             r["log_ls"].append(mean[:, 0]), r["log_sf"].append(mean[:, 1]), r["log_sn"].append(mean[:, 2])
             r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
+            if holdout:
+                pred = post.predict(X_test, Y_test)
+                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
     return {m: {k: np.array(v) for k, v in r.items()} for m, r in res.items()}, data, latent
 
 
 def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n_sets=100, grid=50, n_noise=30, bimodal=False, seed=57,
-        engine=None, hmc=None):
+        engine=None, hmc=None, holdout=0):
     rng = np.random.default_rng(seed)
     out, summary = {}, {"sizes": list(sizes), "noise_vars": list(noise_vars), "n_sets": n_sets, "true": TRUE}
     t0 = time.time()
-    size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed, hmc)
+    size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed, hmc,
+                                        holdout)
     noise_res, noise_data, latent = sweep([(v, n_noise, float(v)) for v in noise_vars], n_sets, 1e4, 5, rng, latent, not bimodal, engine,
-                                          seed, hmc)
+                                          seed, hmc, holdout)
     summary["fit_seconds"] = time.time() - t0
     for name, res in (("size", size_res), ("noise", noise_res)):
         for mode, r in res.items():
             for k, v in r.items():
                 out["%s_%s_%s" % (name, mode, k)] = v
+            if "nlpd" in r:  # held-out points: the cell's data sets averaged, the ML-II plug-in (noise learnt) beside the NUTS mixture
+                tag = "hmc" if mode == "hmc" else "ml2"
+                summary["%s_%s_nlpd" % (name, tag)], summary["%s_%s_rmse" % (name, tag)] = r["nlpd"].mean(1).tolist(), r["rmse"].mean(1).tolist()
             if mode == "hmc":  # the posterior means of the cell's data sets, averaged; beside ML-II's log of the mean fitted lengthscale
                 for k in ("log_ls", "log_sf", "log_sn"):
                     summary["%s_hmc_mean_%s" % (name, k)] = r[k].mean(1).tolist()
@@ -134,9 +154,11 @@ def main(argv=None, engine=None):
     ap.add_argument("--hmc_chains", type=int, default=4)
     ap.add_argument("--hmc_tune", type=int, default=500)
     ap.add_argument("--hmc_draws", type=int, default=500)
+    ap.add_argument("--holdout", type=int, default=0, help="points per data set kept out of the fit and the sampling, and predicted")
     args = ap.parse_args(argv)
     hmc = {"chains": args.hmc_chains, "tune": args.hmc_tune, "draws": args.hmc_draws} if args.hmc else None
-    out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine, hmc=hmc)
+    out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine, hmc=hmc,
+                       holdout=args.holdout)
     os.makedirs(args.out, exist_ok=True)
     base = os.path.join(args.out, "hyperparameter_identification")
     np.savez_compressed(base + ".npz", **out)

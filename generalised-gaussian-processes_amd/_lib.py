@@ -255,8 +255,22 @@ EXACT_NUTS_PROTOTYPES = {
     "sgp_ctx_exact_nuts_batch_advance": (_i32, [_vp] + _EN_ADVANCE),
 }
 
+# the companion library libsgp_exact_predict_hip.so (include/sgp_exact_predict.h): the exact-GP predictive of P problems in one launch
+# and the mixture over the draws of a group
+_EP_BATCH = [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]
+EXACT_PREDICT_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_exact_predict_hip.so")
+EXACT_PREDICT_PROTOTYPES = {
+    "sgp_exact_predict_batch_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "sgp_exact_predict_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_exact_predict_batch": (_i32, _EP_BATCH),
+    "sgp_ctx_exact_predict_batch": (_i32, [_vp] + _EP_BATCH),
+    "sgp_exact_mixture_workspace_bytes": (_sz, [_i64, _i64]),
+    "sgp_exact_mixture_reduce": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _LIB = None
 _EXACT_NUTS_LIB = None
+_EXACT_PREDICT_LIB = None
 
 
 def load_library(path: str | None = None):
@@ -287,27 +301,38 @@ def load_library(path: str | None = None):
     return lib
 
 
+def _load_companion(p, prototypes):
+    load_library()
+    if not os.path.exists(p):
+        raise SgpLibraryError("%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % p)
+    try:
+        lib = C.CDLL(p)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise SgpLibraryError("cannot load %s: %s" % (p, e)) from e
+    for name, (res, args) in prototypes.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise SgpLibraryError("%s does not export %s" % (p, name)) from e
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load_exact_nuts_library():
     """dlopen the companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
     global _EXACT_NUTS_LIB
     if _EXACT_NUTS_LIB is None:
-        load_library()
-        p = EXACT_NUTS_LIB_PATH
-        if not os.path.exists(p):
-            raise SgpLibraryError("%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % p)
-        try:
-            lib = C.CDLL(p)
-        except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
-            raise SgpLibraryError("cannot load %s: %s" % (p, e)) from e
-        for name, (res, args) in EXACT_NUTS_PROTOTYPES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise SgpLibraryError("%s does not export %s" % (p, name)) from e
-            fn.restype = res
-            fn.argtypes = args
-        _EXACT_NUTS_LIB = lib
+        _EXACT_NUTS_LIB = _load_companion(EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES)
     return _EXACT_NUTS_LIB
+
+
+def load_exact_predict_library():
+    """The same for the batched predictive's library (include/sgp_exact_predict.h)."""
+    global _EXACT_PREDICT_LIB
+    if _EXACT_PREDICT_LIB is None:
+        _EXACT_PREDICT_LIB = _load_companion(EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES)
+    return _EXACT_PREDICT_LIB
 
 
 def check(fn_name: str, status: int):

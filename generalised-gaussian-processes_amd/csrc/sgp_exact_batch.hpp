@@ -1,7 +1,8 @@
 // One exact-GP marginal likelihood (value + gradient) inside ONE 256-thread workgroup, the whole problem in that workgroup's LDS:
 // the evaluation sgp_exact_eval_batch (sgp_exact_batch.hip: one problem per workgroup) and the batched device-resident NUTS
 // (sgp_exact_nuts.hip: one chain per workgroup, one evaluation per leapfrog) share.  No inter-workgroup communication, no flags, no
-// spins, no atomics.
+// spins, no atomics.  eb_eval = eb_factor (A, L, u, the value) + eb_invert (L^-1, alpha, tr A^-1) + the gradient; the batched predictive
+// (sgp_exact_predict.hip) runs the first two and goes on from L^-1 and alpha.
 //
 //   A = sf2 k'(X, X) + s2 I ; L = chol(A) ; u = L^-1 y ; F = -1/2 u.u - sum log L_ii - N/2 log 2 pi            (value-only stops here)
 //   L^-1 in place ; alpha = L^-T u ; tr A^-1 = |L^-1|_F^2 ; G = alpha alpha^T - L^-T L^-1 (16 x 16 tiles, never stored)
@@ -62,19 +63,27 @@ __device__ __forceinline__ void eb_load(EbShared<NP>& sh, double* yv, const doub
   for (int i = tid; i < Nr; i += 256) yv[i] = i < N ? Yp[i] : 0.0;
 }
 
-// All 256 threads of the workgroup.  On entry sh.x holds the data set and sh.yv the target (eb_load; not yet synchronised), th = [ls_1..d |
-// sf2 | s2].  Writes out[0..3] = [F, y^T A^-1 y, log|A|, tr A^-1 (NaN without the gradient)], grads[0..d+1] (with_grad) and *info (0, or
-// the 1-based first pivot at which A is not numerically positive definite; then out and grads are NaN).  th / out / grads / info may
-// point to global memory or to LDS outside `sh`; they are written by threads 0..d+1 as the last thing, with no barrier after it.
+// What eb_factor leaves in registers (the same in every thread): F, u.u, sum log L_ii, and `bad` (0, or the 1-based first pivot at which
+// A is not numerically positive definite -- 1 for a hyper-parameter that is not a positive finite number).
+struct EbValue {
+  double F, uu, ld;
+  int bad;
+};
+// ... and eb_invert: tr A^-1 and alpha.alpha
+struct EbInverse {
+  double tr, aa;
+};
+
+// The value half of eb_eval, all 256 threads.  On entry sh.x holds the data set and sh.yv the target (eb_load; not yet synchronised),
+// th = [ls_1..d | sf2 | s2].  Assembles A, factors it (sh.M = L, lower; sh.yv = u = L^-1 y) and returns the scalars of the value; ils
+// receives 1 / ls_q (zero past d).  Ends on block_sum256's barrier.
 template <int KID, int NP>
-__device__ __forceinline__ void eb_eval(EbShared<NP>& sh, const double* __restrict__ th, int N, int d, int with_grad,
-                                        double* __restrict__ out, double* __restrict__ grads, int* __restrict__ info) {
+__device__ __forceinline__ EbValue eb_factor(EbShared<NP>& sh, const double* __restrict__ th, int N, int d, double (&ils)[EB_MAXD]) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, l4 = lane >> 4;
   const int Nr = round_up(N, 16), nb = Nr / 16;
   const double sf2 = th[d], s2 = th[d + 1];
-  double ils[EB_MAXD];
 #pragma unroll
   for (int q = 0; q < EB_MAXD; ++q) ils[q] = q < d ? 1.0 / th[q] : 0.0;
   if (tid == 0) {  // a hyper-parameter that is not a positive finite number (NaN included) is reported as pivot 1: 1 / ls loses a sign
@@ -198,19 +207,18 @@ __device__ __forceinline__ void eb_eval(EbShared<NP>& sh, const double* __restri
   uu = block_sum256(uu, &sh.red[0][0]);
   ld = block_sum256(ld, &sh.red[0][0]);
   const int bad = sh.bad;
-  const double nan = __builtin_nan("");
   const double F = -0.5 * uu - ld - 0.5 * (double)N * 1.8378770664093453;  // log 2 pi
-  if (bad != 0 || !with_grad) {
-    if (tid == 0) {
-      out[0] = bad ? nan : F;
-      out[1] = bad ? nan : uu;
-      out[2] = bad ? nan : 2.0 * ld;
-      out[3] = nan;
-      *info = bad;
-    }
-    if (with_grad && tid < d + 2) grads[tid] = nan;
-    return;
-  }
+  return EbValue{F, uu, ld, bad};
+}
+
+// The inverse, all 256 threads, after an eb_factor that returned bad == 0: sh.M = L^-1 in place (lower), sh.al = alpha = L^-T u (zero
+// in the padding); sh.yv keeps u.  Ends on a barrier: sh.red is free again.
+template <int NP>
+__device__ __forceinline__ EbInverse eb_invert(EbShared<NP>& sh, int N) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int Nr = round_up(N, 16), nb = Nr / 16;
 
   // ---- L^-1 in place, block column by block column from the right:  Inv[below][J] = -Inv[below][below] L[below][J] Inv[J][J] ----
   for (int J = nb - 1; J >= 0; --J) {
@@ -291,7 +299,40 @@ __device__ __forceinline__ void eb_eval(EbShared<NP>& sh, const double* __restri
   }
   tr = block_sum256(tr, &sh.red[0][0]);
   aa = block_sum256(aa, &sh.red[0][0]);
-  __syncthreads();  // red is reused below
+  __syncthreads();  // red is reused by the caller
+  return EbInverse{tr, aa};
+}
+
+// All 256 threads of the workgroup.  On entry sh.x holds the data set and sh.yv the target (eb_load; not yet synchronised), th = [ls_1..d |
+// sf2 | s2].  Writes out[0..3] = [F, y^T A^-1 y, log|A|, tr A^-1 (NaN without the gradient)], grads[0..d+1] (with_grad) and *info (0, or
+// the 1-based first pivot at which A is not numerically positive definite; then out and grads are NaN).  th / out / grads / info may
+// point to global memory or to LDS outside `sh`; they are written by threads 0..d+1 as the last thing, with no barrier after it.
+template <int KID, int NP>
+__device__ __forceinline__ void eb_eval(EbShared<NP>& sh, const double* __restrict__ th, int N, int d, int with_grad,
+                                        double* __restrict__ out, double* __restrict__ grads, int* __restrict__ info) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int Nr = round_up(N, 16), nb = Nr / 16;
+  const double sf2 = th[d];
+  double ils[EB_MAXD];
+  const EbValue val = eb_factor<KID, NP>(sh, th, N, d, ils);
+  const int bad = val.bad;
+  const double F = val.F, uu = val.uu, ld = val.ld;
+  const double nan = __builtin_nan("");
+  if (bad != 0 || !with_grad) {
+    if (tid == 0) {
+      out[0] = bad ? nan : F;
+      out[1] = bad ? nan : uu;
+      out[2] = bad ? nan : 2.0 * ld;
+      out[3] = nan;
+      *info = bad;
+    }
+    if (with_grad && tid < d + 2) grads[tid] = nan;
+    return;
+  }
+  const EbInverse inv = eb_invert<NP>(sh, N);
+  const double tr = inv.tr, aa = inv.aa;
 
   // ---- the lower-triangle 16 x 16 tiles of A^-1 = L^-T L^-1 on the matrix cores, each folded into the d + 1 sums at once ----
   double sq[EB_MAXD];

@@ -1000,6 +1000,68 @@ class HipEngine:
         _lib.check("sgp_exact_eval_batch", st)
         return out[:, 0], out, grads, info
 
+    @property
+    def exact_predict_lib(self):
+        """The companion library of the batched predictive (include/sgp_exact_predict.h), loaded on first use."""
+        return _lib.load_exact_predict_library()
+
+    def exact_predict_batch(self, X, Y, theta, Xs, ix=None, iy=None, ixs=None, kernel="rbf", pred_noise=True):
+        """The exact-GP predictive of P problems in ONE launch (include/sgp_exact_predict.h: sgp_exact_predict_batch).  X: nX x N x d (or
+        N x d), Y: nY x N (or N), Xs: nT x T x d (or T x d), theta: P x (d + 2) rows [ls_1..d | sf2 | s2] -- device tensors; problem p
+        takes data set ix[p], target iy[p] and test set ixs[p] (None: set 0).  Returns device tensors (mean [P, T], var [P, T], info
+        [P] int32); nothing is synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        Xs = Xs if Xs.dim() == 3 else Xs[None]
+        nX, N, d = X.shape
+        nY, (nT, T) = Y.shape[0], Xs.shape[:2]
+        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(theta, "theta"), self._chk(Xs, "Xs")
+        if Y.shape[1] != N or Xs.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
+            raise ValueError("shapes: X %s, Y %s, Xs %s, theta %s (expected theta P x %d)"
+                             % (tuple(X.shape), tuple(Y.shape), tuple(Xs.shape), tuple(theta.shape), d + 2))
+        P = theta.shape[0]
+        ix, iy, ixs = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy"), self._set_index(ixs, nT, P, "ixs")
+        mean, var = self.empty(P, T), self.empty(P, T)
+        info = torch.empty(P, dtype=torch.int32, device=self.device)
+        lib = self.exact_predict_lib
+        ws = self._workspace("exact_predict_batch", lib.sgp_exact_predict_batch_workspace_bytes(P, N, d, T))
+        st = lib.sgp_ctx_exact_predict_batch(
+            self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(Xs), T * d, d, T, self._ptr(ix), self._ptr(iy), self._ptr(ixs),
+            self._ptr(theta), P, N, d, _kernel_id(kernel), 1 if pred_noise else 0, self._ptr(mean), self._ptr(var), self._ptr(info),
+            self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_exact_predict_batch", st)
+        return mean, var, info
+
+    def exact_mixture(self, mean, var, info, offsets, Ytest=None):
+        """The mixture over the draws of each group in ONE launch (sgp_exact_mixture_reduce): rows [offsets[g], offsets[g + 1]) of mean /
+        var (P x T, device) are the draws of group g; ``offsets`` is a host sequence, non-decreasing from 0 to P.  Draws with info != 0
+        are left out.  Returns a dict of device tensors: mean, var [G, T], kept [G] int32, and with ``Ytest`` (G x T) logpdf (the log
+        of the mean density) and mean_logpdf [G, T] (None without).  A group with no draw left is NaN.  Nothing is synchronised."""
+        self._chk(mean, "mean"), self._chk(var, "var")
+        if mean.dim() != 2 or var.shape != mean.shape or info.dtype != torch.int32 or info.device != self.device or \
+                not info.is_contiguous() or info.numel() != mean.shape[0]:
+            raise ValueError("mean and var must be P x T and info P contiguous int32 on %s" % (self.device,))
+        P, T = mean.shape
+        off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        G = off.size - 1
+        if G < 1 or off[0] != 0 or off[-1] != P or np.any(np.diff(off) < 0):
+            raise ValueError("offsets must be non-decreasing from 0 to %d (got %d entries)" % (P, off.size))
+        if Ytest is not None:
+            self._chk(Ytest, "Ytest")
+            if tuple(Ytest.shape) != (G, T):
+                raise ValueError("Ytest must be %d x %d (got %s)" % (G, T, tuple(Ytest.shape)))
+        off_d = torch.as_tensor(off).to(self.device)
+        mm, mv = self.empty(G, T), self.empty(G, T)
+        lp, mlp = (self.empty(G, T), self.empty(G, T)) if Ytest is not None else (None, None)
+        kept = torch.empty(G, dtype=torch.int32, device=self.device)
+        lib = self.exact_predict_lib
+        ws = self._workspace("exact_mixture", lib.sgp_exact_mixture_workspace_bytes(G, T))
+        st = lib.sgp_exact_mixture_reduce(self._ptr(mean), self._ptr(var), self._ptr(info), self._ptr(off_d), G, T, self._ptr(Ytest),
+                                          self._ptr(mm), self._ptr(mv), self._ptr(lp), self._ptr(mlp), self._ptr(kept), self._ptr(ws),
+                                          ws.numel(), self._stream())
+        _lib.check("sgp_exact_mixture_reduce", st)
+        return {"mean": mm, "var": mv, "logpdf": lp, "mean_logpdf": mlp, "kept": kept}
+
     # Evaluations one resident workgroup runs back to back in a launch of ``exact_nuts_batch`` by default (DESIGN 6e-3: 1024 x the
     # measured 138 us per evaluation of one chain at N = 128 keeps the longest launch near 0.14 s); shared among the waves of workgroups
     # when there are more chains than the chip holds at a time.

@@ -10,6 +10,7 @@ from __future__ import annotations
 import math
 import time
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -84,6 +85,25 @@ class ExactNutsResult:
     starts: np.ndarray       # B x chains x (d + 2)
     launches: int            # bounded launches the run took
     wall_clock_secs: float
+    # what the draws were sampled with (``sample_exact_nuts_batch`` fills them in): ``predict`` needs them
+    X: Optional[np.ndarray] = None       # N x d or B x N x d
+    Y: Optional[np.ndarray] = None       # B x N
+    kernel: Optional[str] = None
+    jitter: Optional[float] = None
+    engine: object = None
+
+    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True):
+        """The mixture predictive (``exact_predict.predict_exact_batch``) over every ``thin``-th draw of every chain of each data set."""
+        if self.X is None or self.Y is None or self.kernel is None:
+            raise ValueError("this result does not carry the data it was sampled with (X, Y, kernel, jitter): "
+                             "use predict_exact_batch(X, Y, samples, X_test, ...)")
+        if int(thin) < 1:
+            raise ValueError("thin >= 1 (got %r)" % (thin,))
+        from .exact_predict import predict_exact_batch
+        B, nd = self.samples.shape[0], self.samples.shape[-1]
+        draws = self.samples[:, :, ::int(thin)].reshape(B, -1, nd)
+        return predict_exact_batch(self.X, self.Y, draws, X_test, Y_test, kernel=self.kernel, jitter=self.jitter or 0.0,
+                                   pred_noise=pred_noise, engine=self.engine)
 
     def posterior_mean(self):
         """B x (d + 2): the mean position of every data set over its chains and draws (NaN rows of bad chains left out)."""
@@ -162,4 +182,5 @@ def sample_exact_nuts_batch(X, Y, n_samples: int, tune: int, chains: int = 1, ke
     return ExactNutsResult(traces=traces, samples=samples.reshape(B, chains, n_samples, nd), stats=stats.reshape(B, chains, n_samples, -1),
                            seconds=seconds.reshape(B, chains, n_samples), evaluations=host["evaluations"].reshape(B, chains),
                            draws=host["draws"].reshape(B, chains), info=host["info"].reshape(B, chains), seeds=seeds,
-                           starts=q0.reshape(B, chains, nd), launches=int(r["launches"]), wall_clock_secs=wall)
+                           starts=q0.reshape(B, chains, nd), launches=int(r["launches"]), wall_clock_secs=wall,
+                           X=Xh, Y=Yh, kernel=kernel, jitter=float(jitter), engine=eng)

@@ -1,0 +1,117 @@
+"""The exact-GP mixture predictive over hyper-parameter draws on top of ``engine.exact_predict_batch`` + ``engine.exact_mixture``: what
+the reference does with the draws of models/gpr_hmc.py (one predictive per draw, the RMSE of the mixture mean and the NLPD of the
+mixture) for B data sets x S draws as ONE launch of each kernel (csrc/sgp_exact_predict.hip) and one host copy.
+
+Marginal predictives only (mean and variance per test point); the full-covariance ``MultivariateNormal``s of
+``full_mixture_posterior_predictive`` stay with ``GPR_HMC``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .ml2 import MAX_D, MAX_N, _check_kernel, _dev, _engine
+
+NOISE_FLOOR_VAR, NOISE_FLOOR_SD = 1e-4, 0.01  # the reference's rule: a draw with sig_n^2 < 1e-4 is predicted at sig_n = 0.01
+
+
+@dataclass
+class ExactMixturePredictive:
+    """``predict_exact_batch``'s result (numpy): the mixture over the kept draws of each of B data sets at its T test points."""
+    mean: np.ndarray                   # B x T: the mixture mean
+    var: np.ndarray                    # B x T: the mixture variance (within + between the draws)
+    draw_mean: np.ndarray              # B x S x T
+    draw_var: np.ndarray               # B x S x T
+    info: np.ndarray                   # B x S: 0, or the pivot at which the draw's matrix failed (its rows are NaN; it is left out)
+    kept: np.ndarray                   # B: draws in the mixture
+    logpdf: Optional[np.ndarray]       # B x T: log of the mean over the draws of N(y_t | mu_st, v_st); None without Y_test
+    mean_logpdf: Optional[np.ndarray]  # B x T: the mean over the draws of log N(y_t | mu_st, v_st); None without Y_test
+
+    def nlpd(self, Y_std=1.0):
+        """B values: minus the mean over the test points of ``logpdf``, in the units of the unstandardised targets (+ log Y_std)."""
+        if self.logpdf is None:
+            raise ValueError("nlpd needs the predictive of a call with Y_test")
+        return -self.logpdf.mean(1) + np.log(Y_std)
+
+    def rmse(self, Y_test, Y_std=1.0):
+        """B values: the root mean squared error of the mixture mean."""
+        Y_test = np.asarray(Y_test, dtype=np.float64).reshape(self.mean.shape)
+        return np.sqrt(((self.mean - Y_test) ** 2).mean(1)) * Y_std
+
+
+def _host(a):
+    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+
+
+def predict_theta_batch(X, Y, theta, X_test, Y_test=None, kernel="rbf", pred_noise=True, engine=None) -> ExactMixturePredictive:
+    """The mixture predictive at constrained rows: ``theta`` is B x S x (d + 2), rows [ls_1..d | sf2 | s2], used as they are."""
+    _check_kernel(kernel)
+    eng = _engine(engine)
+    Yh = _host(Y)
+    Yh = Yh[None] if Yh.ndim == 1 else Yh
+    Xh, Xt = _host(X), _host(X_test)
+    Xh = Xh[:, None] if Xh.ndim == 1 else Xh
+    Xt = Xt[:, None] if Xt.ndim == 1 else Xt
+    theta = np.asarray(theta, dtype=np.float64)
+    B, N = Yh.shape
+    d = Xh.shape[-1]
+    shared_x, shared_t = Xh.ndim == 2, Xt.ndim == 2
+    if not 1 <= N <= MAX_N or not 1 <= d <= MAX_D or Xh.shape[-2] != N or (not shared_x and Xh.shape[0] != B):
+        raise ValueError("X must be N x d or B x N x d with 1 <= N <= %d, 1 <= d <= %d, Y B x N (got X %s, Y %s)"
+                         % (MAX_N, MAX_D, Xh.shape, Yh.shape))
+    if Xt.shape[-1] != d or (not shared_t and Xt.shape[0] != B):
+        raise ValueError("X_test must be T x %d or %d x T x %d (got %s)" % (d, B, d, Xt.shape))
+    if theta.ndim != 3 or theta.shape[0] != B or theta.shape[2] != d + 2 or theta.shape[1] < 1:
+        raise ValueError("the draws must be %d x S x %d (got %s)" % (B, d + 2, theta.shape))
+    S, T = theta.shape[1], Xt.shape[-2]
+    if Y_test is not None:
+        Yt = _host(Y_test)
+        Yt = Yt[None] if Yt.ndim == 1 else Yt
+        if Yt.shape != (B, T):
+            raise ValueError("Y_test must be %d x %d (got %s)" % (B, T, Yt.shape))
+    set_of = np.repeat(np.arange(B, dtype=np.int32), S)
+    mean, var, info = eng.exact_predict_batch(_dev(Xh, eng), _dev(Yh, eng), _dev(theta.reshape(B * S, d + 2), eng), _dev(Xt, eng),
+                                              ix=None if shared_x else set_of, iy=set_of, ixs=None if shared_t else set_of,
+                                              kernel=kernel, pred_noise=pred_noise)
+    mix = eng.exact_mixture(mean, var, info, [b * S for b in range(B + 1)], Ytest=None if Y_test is None else _dev(Yt, eng))
+    # one host copy: everything in one float64 buffer (the integer columns are exact in it)
+    parts = [mean.reshape(-1), var.reshape(-1), info.reshape(-1).to(torch.float64), mix["mean"].reshape(-1), mix["var"].reshape(-1),
+             mix["kept"].reshape(-1).to(torch.float64)]
+    if Y_test is not None:
+        parts += [mix["logpdf"].reshape(-1), mix["mean_logpdf"].reshape(-1)]
+    host = torch.cat(parts).cpu().numpy()
+    cuts = np.cumsum([0, B * S * T, B * S * T, B * S, B * T, B * T, B] + ([B * T, B * T] if Y_test is not None else []))
+    seg = [host[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
+    return ExactMixturePredictive(
+        mean=seg[3].reshape(B, T), var=seg[4].reshape(B, T), draw_mean=seg[0].reshape(B, S, T), draw_var=seg[1].reshape(B, S, T),
+        info=seg[2].astype(np.int32).reshape(B, S), kept=seg[5].astype(np.int64),
+        logpdf=seg[6].reshape(B, T) if Y_test is not None else None, mean_logpdf=seg[7].reshape(B, T) if Y_test is not None else None)
+
+
+def constrain_samples(samples, jitter=0.0):
+    """theta rows [ls | sf2 | s2] of unconstrained positions [log ls | log sig_f | log sig_n] (..., d + 2), on a copy: s2 = sig_n^2 +
+    jitter, with the reference's floor (sig_n^2 < 1e-4 -> sig_n = 0.01).  A NaN row stays NaN."""
+    q = np.array(samples, dtype=np.float64)  # (a copy)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.exp(q)
+        sn2 = v[..., -1] ** 2
+        sn2 = np.where(sn2 < NOISE_FLOOR_VAR, NOISE_FLOOR_SD ** 2, sn2)
+        return np.concatenate([v[..., :-2], v[..., -2:-1] ** 2, (sn2 + jitter)[..., None]], -1)
+
+
+def predict_exact_batch(X, Y, samples, X_test, Y_test=None, kernel="rbf", jitter=0.0, pred_noise=True, engine=None) -> ExactMixturePredictive:
+    """The mixture predictive of B exact GPs over S hyper-parameter draws each, on the device: one launch of the predictive kernel
+    (B x S problems, one workgroup each), one of the mixture kernel, one host copy.
+
+    X: N x d (shared) or B x N x d;  Y: B x N (or N);  X_test: T x d (shared) or B x T x d;  Y_test: B x T or None.  ``samples``: B x S
+    x (d + 2) unconstrained positions [log ls | log sig_f | log sig_n] (``ExactNutsResult.samples`` flattened over the chains); theta =
+    [exp, exp^2, exp^2 + jitter].  A draw with sig_n^2 < 1e-4 is predicted at sig_n = 0.01 (the reference's rule), on a copy: ``samples``
+    is not modified.  A row with a NaN (a chain that had no start) fails the kernel's test of theta and is left out of the mixture
+    (``info``, ``kept``), as is a draw whose matrix is not numerically positive definite."""
+    samples = _host(samples)
+    if samples.ndim == 2:
+        samples = samples[None]
+    return predict_theta_batch(X, Y, constrain_samples(samples, jitter), X_test, Y_test, kernel=kernel, pred_noise=pred_noise, engine=engine)

@@ -8,6 +8,7 @@ lives in tensors on the engine's device, every trial point of every problem is o
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -78,6 +79,20 @@ class Ml2Result:
     converged: np.ndarray   # B x (1 + R) bool
     n_iter: np.ndarray      # B x (1 + R): accepted L-BFGS steps
     n_batches: int          # batched evaluations (launches) of the whole fit
+    # what the fit was made with (``fit_ml2`` fills them in): ``predict`` needs them
+    X: Optional[np.ndarray] = None   # N x d or B x N x d
+    Y: Optional[np.ndarray] = None   # B x N
+    kernel: Optional[str] = None
+    engine: object = None
+
+    def predict(self, X_test, Y_test=None, pred_noise=True):
+        """The plug-in predictive at ``theta`` (``exact_predict.ExactMixturePredictive`` with S = 1; theta is constrained already: no
+        exp, no noise floor)."""
+        if self.X is None or self.Y is None or self.kernel is None:
+            raise ValueError("this result does not carry the data it was fitted to (X, Y, kernel)")
+        from .exact_predict import predict_theta_batch
+        return predict_theta_batch(self.X, self.Y, self.theta[:, None, :], X_test, Y_test, kernel=self.kernel, pred_noise=pred_noise,
+                                   engine=self.engine)
 
 
 MEMORY, MAX_ITER, PGTOL, FTOL, ARMIJO = 10, 200, 1e-5, 2.2e-9, 1e-4  # FTOL: scipy's factr = 1e7 times 2.2e-16
@@ -279,7 +294,7 @@ def fit_ml2(X, Y, kernel="rbf", noise="learn", theta0=None, bounds=None, n_resta
     rows = np.arange(B)
     return Ml2Result(theta=theta_all[rows, best], lml=lml_all[rows, best], n_evals=n_evals.reshape(B, S1).sum(1).cpu().numpy(),
                      theta_all=theta_all, lml_all=lml_all, converged=conv, n_iter=n_iter.reshape(B, S1).cpu().numpy(),
-                     n_batches=n_batches)
+                     n_batches=n_batches, X=Xs if Xs.shape[0] == B and B > 1 else Xs[0], Y=Y, kernel=kernel, engine=eng)
 
 
 def identification_data(n_train, n_sets, rng, sig_sd=5.0, lengthscale=2.0, noise_sd=1.0, uniform=True, d=1, n_grid=500, latent=None):
