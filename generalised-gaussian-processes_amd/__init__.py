@@ -19,7 +19,7 @@ from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariation
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
 from .sgp_hmc import (CompositeSgpmcModel, SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments,  # noqa: F401
                       predict_sgpmc, train_sgp_hmc, train_sgp_hmc_composite)
-from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget  # noqa: F401
+from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget, SgpmcTargetBase  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must work without a GPU (build / symbol checks)

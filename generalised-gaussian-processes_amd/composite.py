@@ -23,7 +23,7 @@ import torch
 from ._lib import COMP_LEN
 from .core import CollapsedBound, SgpTimeoutError, few_host_threads
 from .hmc import next_seed, sample_nuts, sample_nuts_device, trace_summary
-from .targets import (_SGPMC_NOISE_FLOOR, SgpmcTarget, _sigmoid, _softplus, _softplus_inv, as_floats, device_sampler_ok, in_range,
+from .targets import (_SGPMC_NOISE_FLOOR, SgpmcTargetBase, _sigmoid, _softplus, _softplus_inv, as_floats, device_sampler_ok, in_range,
                       single_launch_eval, single_launch_ok)
 
 EXPQUAD, MATERN32, MATERN52, RATQUAD, PERIODIC = 0, 1, 2, 3, 4
@@ -247,7 +247,7 @@ def _log_prior(spec, c):
     raise ValueError("unknown prior %r: 'gamma', 'halfnormal' or 'normal'" % (kind,))
 
 
-class CompositeSgpmcTarget:
+class CompositeSgpmcTarget(SgpmcTargetBase):
     """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values of GPflow's ``SGPMC`` with a
     sum-of-products kernel, an optional White term and an optional linear mean function -- the model of experiments/co2_sgpmc.py.
 
@@ -265,36 +265,16 @@ class CompositeSgpmcTarget:
     priors and the chain rule run on the host.  A non-zero ``kuu_factor`` status or a non-finite value gives (-inf, zeros); a device
     time-out raises ``SgpTimeoutError``.  Z is fixed per evaluation (``set_Z`` replaces it); there is no dF/dZ.  One process."""
 
-    LIKELIHOODS = SgpmcTarget.LIKELIHOODS
+    _NAME = "CompositeSgpmcTarget"
 
     def __init__(self, X, y, Z, kernel: CompositeKernel, priors=None, white=None, mean=None, likelihood="gaussian", jitter=1e-4,
                  engine=None):
-        if likelihood not in self.LIKELIHOODS:
-            raise ValueError("CompositeSgpmcTarget takes the likelihoods %s (got %r)" % (", ".join(self.LIKELIHOODS), likelihood))
         if mean not in (None, "linear"):
             raise ValueError("mean is None or 'linear' (got %r)" % (mean,))
         if white is not None and not float(white) > 0.0:
             raise ValueError("white is None (no White term) or its positive start value")
-        if engine is None:
-            from .engine import HipEngine
-            engine = HipEngine(X.device if X.is_cuda else None)
-        self.engine = engine
-        if X.dim() == 1:
-            X = X[:, None]
-        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
-        yh = y.detach().to(dtype=torch.float64, device="cpu").reshape(-1)
-        if self.X.shape[0] != yh.shape[0]:
-            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], yh.shape[0]))
-        if likelihood in ("bernoulli", "bernoulli_logit"):   # {0, 1} or {-1, +1} labels -> {-1, +1}
-            if not bool(((yh == 0.0) | (yh == 1.0) | (yh == -1.0)).all()) or (bool((yh == 0.0).any()) and bool((yh == -1.0).any())):
-                raise ValueError("Bernoulli labels must be {0, 1} or {-1, +1}")
-            if bool((yh == 0.0).any()):
-                yh = 2.0 * yh - 1.0
-        elif likelihood == "poisson" and not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
-            raise ValueError("Poisson counts must be non-negative integers")
-        self.y = yh.to(engine.device).contiguous()
-        self.likelihood, self.kernel, self.jitter, self.mean = likelihood, kernel, float(jitter), mean
-        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+        self._intake(X, y, likelihood, engine)
+        self.kernel, self.jitter, self.mean = kernel, float(jitter), mean
         self.priors = dict(priors or {})
         self._structure = kernel.block()
         # the theta entries: (name, role, block slot or coefficient index, start value); roles amp / ls / aux / white / noise are positive
@@ -319,24 +299,12 @@ class CompositeSgpmcTarget:
             if name not in {e[0] for e in ent}:
                 raise ValueError("a prior is given for %r, which this target does not sample (%s)" % (name, ", ".join(self.names)))
             _log_prior(self.priors[name], 1.0)
-        self.n_evals = 0
-        self._t_keep = None
         self.set_Z(Z)
 
     @property
     def names(self):
         """The theta entries in the order of q (``mean_A`` once per input dimension), without ``V``."""
         return [e[0] for e in self._entries]
-
-    def set_Z(self, Z):
-        if Z.dim() == 1:
-            Z = Z[:, None]
-        Z = Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
-        if Z.shape[1] != self.d:
-            raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
-        self.Z = Z
-        self.M = int(Z.shape[0])
-        self.ndim = self.n_theta + self.M
 
     def start(self):
         """[UPSTREAM] GPflow's defaults as recalled: variances, lengthscales, alpha, white and the likelihood variance 1, A = 1, b = 0,
@@ -378,11 +346,6 @@ class CompositeSgpmcTarget:
         c["V"] = np.asarray(x[self.n_theta:], dtype=np.float64)
         c["kernel"] = self.kernel.with_values([math.sqrt(block[s]) if r == "amp" else block[s] for _, s, r in self.kernel.free_parameters()])
         return c
-
-    def _t_for(self):
-        if self._t_keep is None or self._t_keep.numel() < ((max(self.N, 1) + 255) // 256 * 256) * ((self.M + 127) // 128 * 128):
-            self._t_keep = self.engine.kfu_buffer(self.N, self.M)
-        return self._t_keep
 
     def _eval(self, q, want_grad):
         x = as_floats(q)

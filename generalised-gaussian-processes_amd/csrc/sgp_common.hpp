@@ -181,6 +181,44 @@ __device__ __forceinline__ double block_sum256(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// The last-workgroup reduction of K sums over a grid of 256-thread blocks (blockIdx.x only).  s[] = this workgroup's K sums (from
+// block_sum256), part = K doubles per workgroup, counter = one int that is 0 when the launch starts, red = block_sum256's 4 LDS words,
+// last = one more LDS word.  The partials are published with an agent-scope release and a ticket; the workgroup that draws the last
+// ticket adds them up in index order, so the totals do not depend on which workgroup that was.  Returns true in every thread of that
+// workgroup, with the totals in s[]; false in all others.  Call from every thread of the block.
+template <int K>
+__device__ __forceinline__ bool last_block_sums(double (&s)[K], double* part, int* __restrict__ counter, double* red, double* last) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) part[K * (size_t)blockIdx.x + k] = s[k];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool is_last = ticket == (int)gridDim.x - 1;
+    if (is_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *last = is_last ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  if (*last == 0.0) return false;
+  // The other workgroups' partials: thread 0 made the agent-scope acquire, the barrier orders the other 255 threads behind it.  The
+  // loads are agent-scope atomic loads all the same (`part` is not __restrict__: it is read after foreign writes), so that neither the
+  // compiler can move them ahead of the ticket nor a line this CU cached earlier can serve them.
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = 0.0;
+  for (int i = tid; i < (int)gridDim.x; i += 256) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] += __hip_atomic_load(part + K * (size_t)i + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = block_sum256(s[k], red);
+  return true;
+}
+
 // Workspace carving: 256-byte aligned bump allocator over the caller's scratch buffer.
 struct Carver {
   char* base;

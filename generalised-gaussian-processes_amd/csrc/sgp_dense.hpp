@@ -28,6 +28,21 @@ struct GemmDesc {
   bool mirror = false;      // with lower_only: every tile below the diagonal is also stored transposed (a symmetric product computed once)
 };
 void gemm(const GemmDesc& g, hipStream_t st);
+// The sandwich of an adjoint through the whitening: R = L^-T S' L^-1 (all Mp x Mp, ld Mp; Linv = L^-1 lower triangular, T = scratch).
+// Returns the blocks a closing launch gives to cropping sym(R) to M x M: 256 entries per block, 2048 blocks at the most.
+static inline int linv_sandwich(const double* Sp, const double* Linv, int M, int Mp, double* T, double* R, hipStream_t st) {
+  const int64_t ld = Mp;
+  GemmDesc t1;  // T = S' L^-1: L^-1 is lower triangular, k starts at the tile's column range
+  t1.A = Sp; t1.lda = ld; t1.B = Linv; t1.ldb = ld; t1.C = T; t1.ldc = ld;
+  t1.m = Mp; t1.n = Mp; t1.k = Mp; t1.klo_mask = 2;
+  gemm(t1, st);
+  GemmDesc t2;  // R = L^-T T: k starts at the tile's row range
+  t2.A = Linv; t2.lda = ld; t2.ta = true; t2.B = T; t2.ldb = ld; t2.C = R; t2.ldc = ld;
+  t2.m = Mp; t2.n = Mp; t2.k = Mp; t2.klo_mask = 1;
+  gemm(t2, st);
+  const int64_t g = ((int64_t)M * M + 255) / 256;
+  return (int)(g < 2048 ? g : 2048);
+}
 // Condition estimate of a factored matrix (sgp_tail.hip): cond_stats fills `scratch` (cond_scratch_doubles(M) doubles per matrix) from
 // the factor L and its explicit inverse, cond_gate reports est = lambda_max_estimate / lambda_min_estimate > limit into info[s].
 size_t cond_scratch_doubles(int M);

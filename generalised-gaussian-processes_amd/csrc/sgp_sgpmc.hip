@@ -1,8 +1,9 @@
 // The M x M tail of SGPMC (Hensman et al. 2015; the reference's models/sgp_hmc.py:38-43, GPflow's SGPMC with a Gaussian likelihood):
 // the joint log-density of the whitened inducing values v and the data given v, from the whitened sufficient statistics
 // [W | u | yy | kappa] of pass 1 (include/sgp.h states the density and its adjoints).  Nothing is factored here: L^-1 comes from
-// sgp_kuu_factor, so the tail is one elementwise / matrix-vector launch, the sandwich L^-T S' L^-1 (two gemm() calls with the
-// triangular masks bound_impl uses for its own sandwich) and one closing launch -- four launches, two without the adjoints.
+// sgp_kuu_factor, so the tail is one elementwise / matrix-vector launch, the sandwich L^-T S' L^-1 (linv_sandwich of sgp_dense.hpp: two
+// gemm() calls with triangular masks) and one closing launch -- four launches, two without the adjoints.  Both extern "C" tails are
+// sgpmc_tail<LIK> below.
 #include "sgp_common.hpp"
 #include "sgp_dense.hpp"
 
@@ -164,6 +165,26 @@ static SgpmcWs carve_sgpmc(void* ws, int Mp) {
   return w;
 }
 
+// Both tails: the shared checks (every SGP_ERR_ARG ahead of SGP_ERR_DIM; a tail's own stand in front of this call), the carve and the
+// launches.  (W, u, yy, kappa) are the whitened statistics, or with LIK (G, g, the row pass's three sums, nullptr).
+template <bool LIK>
+static int sgpmc_tail(const double* W, const double* u, const double* yy, const double* kappa, const double* v, double s2, int64_t N, int M,
+                      int with_adjoints, double* out, double* vbar, double* Cw, double* bbar, double* Kuubar, const double* kuu_linv,
+                      void* ws, size_t ws_bytes, sgp_stream_t stream) {
+  if (!yy || !v || !out || M <= 0 || N < 0) return SGP_ERR_ARG;
+  if (with_adjoints && (!vbar || !bbar || !Kuubar || !kuu_linv)) return SGP_ERR_ARG;
+  if (M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
+  const int Mp = padded_m(M);
+  SgpmcWs w = carve_sgpmc(ws, Mp);
+  if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int adj = with_adjoints ? 1 : 0;
+  sgpmc_mid_kernel<LIK><<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(W, u, v, kuu_linv, M, Mp, s2, adj, w.hvec, w.rows4, Cw, w.Sp, w.t);
+  const int nA = adj ? linv_sandwich(w.Sp, kuu_linv, M, Mp, w.T, w.R, st) : 0;
+  sgpmc_out_kernel<LIK><<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, yy, kappa, M, Mp, s2, (double)N, nA, Kuubar, bbar, vbar, out);
+  return check_launch();
+}
+
 }  // namespace sgp
 
 using namespace sgp;
@@ -177,62 +198,17 @@ extern "C" int sgp_sgpmc_from_whitened_stats(const double* W, const double* u, c
                                              double s2, int64_t N, int M, int with_adjoints, double* out, double* vbar, double* Cw,
                                              double* bbar, double* Kuubar, const double* kuu_linv, void* ws, size_t ws_bytes,
                                              sgp_stream_t stream) {
-  if (!W || !u || !yy || !kappa || !v || !out || M <= 0 || N < 0 || !(s2 > 0.0)) return SGP_ERR_ARG;
-  if (with_adjoints && (!vbar || !Cw || !bbar || !Kuubar || !kuu_linv)) return SGP_ERR_ARG;
-  if (M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
-  const int Mp = padded_m(M);
-  SgpmcWs w = carve_sgpmc(ws, Mp);
-  if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int adj = with_adjoints ? 1 : 0;
-  sgpmc_mid_kernel<false><<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(W, u, v, kuu_linv, M, Mp, s2, adj, w.hvec, w.rows4, Cw, w.Sp, w.t);
-  int nA = 0;
-  if (adj) {
-    const int64_t ld = Mp;
-    GemmDesc t1;  // T = S' L^-1: L^-1 is lower triangular, k starts at the tile's column range
-    t1.A = w.Sp; t1.lda = ld; t1.B = kuu_linv; t1.ldb = ld; t1.C = w.T; t1.ldc = ld;
-    t1.m = Mp; t1.n = Mp; t1.k = Mp; t1.klo_mask = 2;
-    gemm(t1, st);
-    GemmDesc t2;  // R = L^-T T: k starts at the tile's row range
-    t2.A = kuu_linv; t2.lda = ld; t2.ta = true; t2.B = w.T; t2.ldb = ld; t2.C = w.R; t2.ldc = ld;
-    t2.m = Mp; t2.n = Mp; t2.k = Mp; t2.klo_mask = 1;
-    gemm(t2, st);
-    const int64_t g = ((int64_t)M * M + 255) / 256;
-    nA = (int)(g < 2048 ? g : 2048);
-  }
-  sgpmc_out_kernel<false><<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, yy, kappa, M, Mp, s2, (double)N, nA, Kuubar, bbar, vbar, out);
-  return check_launch();
+  if (!W || !u || !kappa || !(s2 > 0.0) || (with_adjoints && !Cw)) return SGP_ERR_ARG;
+  return sgpmc_tail<false>(W, u, yy, kappa, v, s2, N, M, with_adjoints, out, vbar, Cw, bbar, Kuubar, kuu_linv, ws, ws_bytes, stream);
 }
 
-// The tail behind sgp_sgpmc_lik_rows: the same four launches on (G, g) in place of (W, u).
+// The tail behind sgp_sgpmc_lik_rows: the same four launches on (G, g) in place of (W, u), with s2 = 1.
 extern "C" size_t sgp_sgpmc_lik_workspace_bytes(int M) { return sgp_sgpmc_workspace_bytes(M); }
 
 extern "C" int sgp_sgpmc_lik_tail(const double* rows_out, const double* G, const double* g, const double* v, int64_t N, int M,
                                   int with_adjoints, double* out, double* vbar, double* bbar, double* Kuubar, const double* kuu_linv,
                                   void* ws, size_t ws_bytes, sgp_stream_t stream) {
-  if (!rows_out || !v || !out || M <= 0 || N < 0) return SGP_ERR_ARG;
-  if (with_adjoints && (!G || !g || !vbar || !bbar || !Kuubar || !kuu_linv)) return SGP_ERR_ARG;
-  if (M > SGP_MAX_INDUCING) return SGP_ERR_DIM;
-  const int Mp = padded_m(M);
-  SgpmcWs w = carve_sgpmc(ws, Mp);
-  if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int adj = with_adjoints ? 1 : 0;
-  sgpmc_mid_kernel<true><<<Mp / 16 + (adj ? Mp / 64 : 0), 1024, 0, st>>>(G, g, v, kuu_linv, M, Mp, 1.0, adj, w.hvec, w.rows4, nullptr, w.Sp, w.t);
-  int nA = 0;
-  if (adj) {
-    const int64_t ld = Mp;
-    GemmDesc t1;  // T = S' L^-1
-    t1.A = w.Sp; t1.lda = ld; t1.B = kuu_linv; t1.ldb = ld; t1.C = w.T; t1.ldc = ld;
-    t1.m = Mp; t1.n = Mp; t1.k = Mp; t1.klo_mask = 2;
-    gemm(t1, st);
-    GemmDesc t2;  // R = L^-T T
-    t2.A = kuu_linv; t2.lda = ld; t2.ta = true; t2.B = w.T; t2.ldb = ld; t2.C = w.R; t2.ldc = ld;
-    t2.m = Mp; t2.n = Mp; t2.k = Mp; t2.klo_mask = 1;
-    gemm(t2, st);
-    const int64_t gr = ((int64_t)M * M + 255) / 256;
-    nA = (int)(gr < 2048 ? gr : 2048);
-  }
-  sgpmc_out_kernel<true><<<nA + 1, 256, 0, st>>>(w.R, w.t, w.hvec, v, w.rows4, rows_out, nullptr, M, Mp, 1.0, (double)N, nA, Kuubar, bbar, vbar, out);
-  return check_launch();
+  if (with_adjoints && (!G || !g)) return SGP_ERR_ARG;
+  return sgpmc_tail<true>(G, g, rows_out, nullptr, v, 1.0, N, M, with_adjoints, out, vbar, nullptr, bbar, Kuubar, kuu_linv, ws, ws_bytes,
+                          stream);
 }

@@ -1,9 +1,11 @@
 // The row pass of SGPMC with a non-conjugate likelihood (include/sgp.h: sgp_sgpmc_lik_rows): from T = K'_fu L^-T of the whitened rows
 // layout, per datum the conditional moments  mu_n = a_n.v,  var_n = sf2 - |a_n|^2  (a_n = sf2 T_n), the likelihood layer of
-// sgp_lik.hpp, and the two M-sized adjoints  g = sum_n dmu_n a_n,  G = sum_n dv_n a_n a_n^T.  The eighth user of the host-side frame of
-// sgp_stream.hpp; assembly, T = K' R, the contraction, tpart_kernel and the fixed-order reductions are sgp_suffstats_fwd.hip's own:
-//   prologue, assembly, T = K' R                              the existing kernels (the unweighted T^T T of the Gaussian path is not run)
+// sgp_lik.hpp, and the two M-sized adjoints  g = sum_n dmu_n a_n,  G = sum_n dv_n a_n a_n^T.  A user of the host-side frame of
+// sgp_stream.hpp: the plan is rows_plan, the start of the pass stream_rows_start (both shared with sgp_sgpmc_mc.hip); the contraction,
+// tpart_kernel and the fixed-order reductions are sgp_suffstats_fwd.hip's own:
+//   stream_rows_start                                         prologue, R = L^-T, assembly, T = K' R (the unweighted T^T T of the Gaussian path is not run)
 //   sgpmc_lik_rows_kernel                                     reads T once: moments + likelihood, dmu, dv, [sum ell | sum ds2 | sum dv]
+//                                                             (closed by last_block_sums of sgp_common.hpp; zero_ints ahead of it)
 //   -- a value-only call ends here --
 //   tpart_kernel(ys := dmu) + the b reduction                 g
 //   sgpmc_lik_scale_kernel(+1), contraction, slab reduction   T_n <- sqrt(-dv_n) T_n;  G = -sf2^2 S^T S  (dv <= 0: log-concave likelihoods)
@@ -19,8 +21,8 @@ namespace sgp {
 
 // One workgroup per ASM_ROWS rows.  Phase 1: wave w owns rows [64 w, 64 w + 64), four at a time; a lane reads 16 bytes of each row per
 // step of 128 columns, v comes from LDS, the two sums of a row are closed by the wave butterfly.  Phase 2: one thread per row runs the
-// likelihood.  The per-workgroup partials [ell | ds2 | dv] are published with an agent-scope release and a ticket; the workgroup that
-// draws the last ticket adds them up in index order, so the sums do not depend on which workgroup that was.
+// likelihood.  The per-workgroup partials [ell | ds2 | dv] are added up by last_block_sums (sgp_common.hpp): in index order, by the
+// workgroup that draws the last ticket.
 // LDS (dynamic, one array): v (Mp) | t.v of the rows (256) | |t|^2 of the rows (256) | block_sum256's 4 words | the "I am last" word.
 // The rows are a_n = scale T_n and k(x_n, x_n) = knn: (sf2, sf2) for the unit-amplitude T of a stationary kernel, (1, kdiag + white) for
 // the full-amplitude T of a composite one (sgp_sgpmc_comp.hip), which also brings the optional mean function `mean` (N, added to mu)
@@ -85,46 +87,19 @@ __global__ __launch_bounds__(256) void sgpmc_lik_rows_kernel(const double* __res
   }
   dmu_pad[n] = gm;
   dv_pad[n] = gv;
-  const double se = block_sum256(ell, red);
-  const double ss = block_sum256(gs, red);
-  const double sd = block_sum256(gv, red);
+  double s[3];
+  s[0] = block_sum256(ell, red);
+  s[1] = block_sum256(gs, red);
+  s[2] = block_sum256(gv, red);
+  if (!last_block_sums(s, part, counter, red, last)) return;
   if (tid == 0) {
-    part[3 * (size_t)blockIdx.x] = se;
-    part[3 * (size_t)blockIdx.x + 1] = ss;
-    part[3 * (size_t)blockIdx.x + 2] = sd;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool is_last = ticket == (int)gridDim.x - 1;
-    if (is_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *last = is_last ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  if (*last == 0.0) return;
-  // The other workgroups' partials: thread 0 made the agent-scope acquire, the barrier orders the other 255 threads behind it.  The
-  // loads are agent-scope atomic loads all the same (`part` is not __restrict__: it is read after foreign writes), so that neither the
-  // compiler can move them ahead of the ticket nor a line this CU cached earlier can serve them.
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  for (int i = tid; i < (int)gridDim.x; i += 256) {
-    a0 += __hip_atomic_load(part + 3 * (size_t)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a1 += __hip_atomic_load(part + 3 * (size_t)i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a2 += __hip_atomic_load(part + 3 * (size_t)i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  a0 = block_sum256(a0, red);
-  a1 = block_sum256(a1, red);
-  a2 = block_sum256(a2, red);
-  if (tid == 0) {
-    out[0] = a0;
-    out[1] = a1;
-    out[2] = a2;
+    out[0] = s[0];
+    out[1] = s[1];
+    out[2] = s[2];
   }
 }
 
-// the same outputs for an empty shard
+// the same outputs for an empty shard (of every row pass that writes [sum ell | sum ds2 | sum dv])
 __global__ void sgpmc_lik_empty_kernel(double* __restrict__ out) {
   if (threadIdx.x < SGP_SGPMC_LIK_OUT_LEN) out[threadIdx.x] = 0.0;
 }
@@ -189,13 +164,6 @@ static LikRowsWs carve_lik_rows(void* ws, const StreamPlan& p) {
   w.bytes = w.wh.bytes + c.used();
   return w;
 }
-// the plan of a call: all of T is the caller's, one super-chunk; false where the shard's K'_fu does not fit the budget of one
-static bool lik_rows_plan(int64_t N, int M, int d, StreamPlan& p) {
-  p = make_stream_plan(N, M, d);
-  if (p.sc_rows < p.Npad) return false;
-  p.sc_rows = p.Npad;
-  return true;
-}
 
 }  // namespace sgp
 
@@ -204,7 +172,7 @@ using namespace sgp;
 extern "C" size_t sgp_sgpmc_lik_rows_workspace_bytes(int64_t N, int M, int d) {
   if (!stream_shape_ok(N, M, d)) return 0;
   StreamPlan p;
-  if (!lik_rows_plan(N, M, d, p)) return 0;
+  if (!rows_plan(N, M, d, p)) return 0;
   return carve_lik_rows(nullptr, p).bytes;
 }
 
@@ -219,7 +187,7 @@ extern "C" int sgp_sgpmc_lik_rows(const double* X, int64_t ldx, const double* y,
   if (N > 0 && (!dmu || !dv)) return SGP_ERR_ARG;
   if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, v, out, T_out}, X, ldx, y, ldz, N, M, d, kernel_id, false)) return bad;
   StreamPlan p;
-  if (!lik_rows_plan(N, M, d, p)) return SGP_ERR_WORKSPACE;
+  if (!rows_plan(N, M, d, p)) return SGP_ERR_WORKSPACE;
   LikRowsWs w = carve_lik_rows(ws, p);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -232,14 +200,8 @@ extern "C" int sgp_sgpmc_lik_rows(const double* X, int64_t ldx, const double* y,
     }
     return check_launch();
   }
-  stream_prologue(p, make_kern_args(inv_ls, sf2, d), X, ldx, y, Z, ldz, N, M, f.Xs, f.ys, f.Zs, f.yypart, st);
-  transpose_square(kuu_linv, p.Mp, w.wh.R, st);  // R = L^-T as a plain row-major operand
+  stream_rows_start(p, kernel_id, make_kern_args(inv_ls, sf2, d), X, ldx, y, Z, ldz, N, M, kuu_linv, w.wh, T_out, st);
   zero_ints(w.counter, 1, st);
-  stream_assemble(p, kernel_id, f.Xs, f.ys, f.Zs, 0, p.Npad, N, M, f.Kfu, f.bpart, st);
-  GemmDesc t;  // T = K' R: column block c of the upper-triangular R needs k < its end only
-  t.A = f.Kfu; t.lda = p.Mp; t.B = w.wh.R; t.ldb = p.Mp; t.C = T_out; t.ldc = p.Mp;
-  t.m = (int)p.Npad; t.n = p.Mp; t.k = p.Mp; t.khi_mask = 2;
-  gemm(t, st);
   sgpmc_lik_rows_launch(T_out, y, nullptr, v, N, p.Npad, M, p.Mp, sf2, sf2, s2, likelihood_id, dmu, dv, nullptr, nullptr, w.dmu_pad,
                         w.dv_pad, w.part, w.counter, out, st);
   if (!want_adjoints) return check_launch();

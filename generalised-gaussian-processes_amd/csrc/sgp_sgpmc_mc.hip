@@ -1,6 +1,7 @@
 // SGPMC with the multi-class robust-max likelihood (include/sgp.h: sgp_sgpmc_mc_rows, sgp_sgpmc_mc_tail): C latent GPs that share one
 // kernel and one Z, whitened inducing values V = [v_1 .. v_C] (C x M, class-major).  Assembly, T = K' R, the contraction and the fixed-order
-// slab reduction are sgp_suffstats_fwd.hip's own, the two triangular products of the tail sgp_dense.hip's; new here:
+// slab reduction are sgp_suffstats_fwd.hip's own (the row pass starts with stream_rows_start, as sgp_sgpmc_lik.hip's), the sandwich of
+// the tail is linv_sandwich (sgp_dense.hpp), an empty shard's outputs are sgpmc_lik_empty_launch's; new here:
 //   mc_pad_v_kernel                                    V zero-padded to C x Mp
 //   mc_rows_kernel                                     reads T ONCE for all classes: the C means and the variance of every datum, V staged
 //                                                      through LDS by column blocks; the likelihood; dmu (C x N), dv, [sum ell | 0 | sum dv]
@@ -17,6 +18,7 @@
 #include "sgp_dense.hpp"
 #include "sgp_ctx.hpp"
 #include "sgp_lik.hpp"
+#include "sgp_sgpmc_lik.hpp"
 
 namespace sgp {
 
@@ -46,8 +48,8 @@ __global__ __launch_bounds__(256) void mc_pad_v_kernel(const double* __restrict_
 // One workgroup per MC_ROWS rows.  Phase 1, per stage of CB columns: V's block goes to LDS (CT x CB), wave w owns rows [32 w, 32 w + 32),
 // four at a time; a lane reads 16 bytes of each row per step of 128 columns and feeds CT dot products per row from LDS; the CT + 1 sums of
 // a row are closed by the wave butterfly and added to the row's LDS slots in stage order.  Phase 2: one thread per row runs the likelihood
-// on its LDS slots.  The partials [ell | 0 | dv] are published with a ticket as in sgpmc_lik_rows_kernel: the last workgroup adds them up
-// in index order.  y == nullptr: moments only (mu_out, var_out), no ticket, nothing else written.
+// on its LDS slots.  The partials [ell | dv] are added up by last_block_sums (sgp_common.hpp), in index order.  y == nullptr: moments
+// only (mu_out, var_out), no ticket, nothing else written.
 // LDS (dynamic): V stage (CT x CB) | means and |t|^2 (MC_ROWS x SA) | dmu (MC_ROWS x SA) | block_sum256's 4 words | the "I am last" word
 template <int CT>
 __global__ __launch_bounds__(256) void mc_rows_kernel(const double* __restrict__ T, const double* __restrict__ y,
@@ -142,41 +144,15 @@ __global__ __launch_bounds__(256) void mc_rows_kernel(const double* __restrict__
     }
   }
   if (!y) return;
-  const double se = block_sum256(ell, red);
-  const double sd = block_sum256(gv, red);
+  double s[2];
+  s[0] = block_sum256(ell, red);
+  s[1] = block_sum256(gv, red);
+  if (!last_block_sums(s, part, counter, red, last)) return;
   if (tid == 0) {
-    part[2 * (size_t)blockIdx.x] = se;
-    part[2 * (size_t)blockIdx.x + 1] = sd;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool is_last = ticket == (int)gridDim.x - 1;
-    if (is_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *last = is_last ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  if (*last == 0.0) return;
-  // (agent-scope atomic loads of the foreign partials, as in sgpmc_lik_rows_kernel)
-  double a0 = 0.0, a1 = 0.0;
-  for (int i = tid; i < (int)gridDim.x; i += 256) {
-    a0 += __hip_atomic_load(part + 2 * (size_t)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a1 += __hip_atomic_load(part + 2 * (size_t)i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  a0 = block_sum256(a0, red);
-  a1 = block_sum256(a1, red);
-  if (tid == 0) {
-    out[0] = a0;
+    out[0] = s[0];
     out[1] = 0.0;
-    out[2] = a1;
+    out[2] = s[1];
   }
-}
-
-__global__ void mc_empty_kernel(double* __restrict__ out) {
-  if (threadIdx.x < SGP_SGPMC_LIK_OUT_LEN) out[threadIdx.x] = 0.0;
 }
 
 // gpart[(block b, class c)][m] = sum over the block's ASM_ROWS rows of T[n][m] dmu_c[n], all classes from one read of T;
@@ -326,12 +302,6 @@ static McRowsWs carve_mc_rows(void* ws, const StreamPlan& p, int M, int C) {
   w.bytes = w.wh.bytes + c.used();
   return w;
 }
-static bool mc_rows_plan(int64_t N, int M, int d, StreamPlan& p) {
-  p = make_stream_plan(N, M, d);
-  if (p.sc_rows < p.Npad) return false;
-  p.sc_rows = p.Npad;
-  return true;
-}
 
 // ---- the tail ------------------------------------------------------------------------------------------------------------------
 // Launch 1 (adjoints only), two jobs by block range as sgpmc_mid_kernel:
@@ -440,7 +410,7 @@ using namespace sgp;
 extern "C" size_t sgp_sgpmc_mc_rows_workspace_bytes(int64_t N, int M, int d, int C) {
   if (!stream_shape_ok(N, M, d) || !mc_classes_ok(C)) return 0;
   StreamPlan p;
-  if (!mc_rows_plan(N, M, d, p)) return 0;
+  if (!rows_plan(N, M, d, p)) return 0;
   return carve_mc_rows(nullptr, p, M, C).bytes;
 }
 
@@ -457,13 +427,13 @@ extern "C" int sgp_sgpmc_mc_rows(const double* X, int64_t ldx, const double* y, 
   // (the shared check asks for the data rows of a non-empty shard: X stands in for an absent y, which it never reads)
   if (const int bad = check_stream_args({Z, inv_ls, kuu_linv, V, T_out}, X, ldx, y ? y : X, ldz, N, M, d, kernel_id, false)) return bad;
   StreamPlan p;
-  if (!mc_rows_plan(N, M, d, p)) return SGP_ERR_WORKSPACE;
+  if (!rows_plan(N, M, d, p)) return SGP_ERR_WORKSPACE;
   McRowsWs w = carve_mc_rows(ws, p, M, C);
   if (!ws || ws_bytes < w.bytes) return SGP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const FwdWs& f = w.wh.f;
   if (p.Npad == 0) {
-    mc_empty_kernel<<<1, 64, 0, st>>>(out);
+    sgpmc_lik_empty_launch(out, st);
     if (want_adjoints) {
       fill_zero(G, (size_t)M * M, st);
       fill_zero(g, (size_t)C * M, st);
@@ -472,15 +442,9 @@ extern "C" int sgp_sgpmc_mc_rows(const double* X, int64_t ldx, const double* y, 
   }
   const int CT = mc_ct(C), CB = mc_cb(CT, p.Mp);
   // the prologue copies "y" into the padded ys the assembly's K'^T y partials read: neither is used here, any N readable doubles do
-  stream_prologue(p, make_kern_args(inv_ls, sf2, d), X, ldx, y ? y : X, Z, ldz, N, M, f.Xs, f.ys, f.Zs, f.yypart, st);
-  transpose_square(kuu_linv, p.Mp, w.wh.R, st);  // R = L^-T as a plain row-major operand
+  stream_rows_start(p, kernel_id, make_kern_args(inv_ls, sf2, d), X, ldx, y ? y : X, Z, ldz, N, M, kuu_linv, w.wh, T_out, st);
   zero_ints(w.counter, 1, st);
   mc_pad_v_kernel<<<(C * p.Mp + 255) / 256, 256, 0, st>>>(V, C, M, p.Mp, w.Vp);
-  stream_assemble(p, kernel_id, f.Xs, f.ys, f.Zs, 0, p.Npad, N, M, f.Kfu, f.bpart, st);
-  GemmDesc t;  // T = K' R: column block c of the upper-triangular R needs k < its end only
-  t.A = f.Kfu; t.lda = p.Mp; t.B = w.wh.R; t.ldb = p.Mp; t.C = T_out; t.ldc = p.Mp;
-  t.m = (int)p.Npad; t.n = p.Mp; t.k = p.Mp; t.khi_mask = 2;
-  gemm(t, st);
   static const GHTable gh = make_gh();
   const unsigned rgrid = (unsigned)(p.Npad / MC_ROWS);
   mc_dispatch(CT, [&](auto ct) {
@@ -537,17 +501,7 @@ extern "C" int sgp_sgpmc_mc_tail(const double* rows_out, const double* G, const 
   int nA = 0;
   if (with_adjoints) {
     mc_mid_kernel<<<Mp / 16 + C * (Mp / 64), 1024, 0, st>>>(G, g, V, kuu_linv, C, M, Mp, w.Sp, w.t);
-    const int64_t ld = Mp;
-    GemmDesc t1;  // T = S' L^-1: L^-1 is lower triangular, k starts at the tile's column range
-    t1.A = w.Sp; t1.lda = ld; t1.B = kuu_linv; t1.ldb = ld; t1.C = w.T; t1.ldc = ld;
-    t1.m = Mp; t1.n = Mp; t1.k = Mp; t1.klo_mask = 2;
-    gemm(t1, st);
-    GemmDesc t2;  // R = L^-T T: k starts at the tile's row range
-    t2.A = kuu_linv; t2.lda = ld; t2.ta = true; t2.B = w.T; t2.ldb = ld; t2.C = w.R; t2.ldc = ld;
-    t2.m = Mp; t2.n = Mp; t2.k = Mp; t2.klo_mask = 1;
-    gemm(t2, st);
-    const int64_t gr = ((int64_t)M * M + 255) / 256;
-    nA = (int)(gr < 2048 ? gr : 2048);
+    nA = linv_sandwich(w.Sp, kuu_linv, M, Mp, w.T, w.R, st);
   }
   mc_out_kernel<<<nA + 1, 256, 0, st>>>(w.R, w.t, g, V, rows_out, C, M, Mp, (double)N, nA, Kuubar, bbar, vbar, out);
   return check_launch();

@@ -250,6 +250,17 @@ struct WhRowsWs {
   size_t bytes;
 };
 WhRowsWs carve_wh_rows(void* ws, const StreamPlan& p, bool caller_t);
+// the plan of a row pass whose T is all the caller's, in one super-chunk; false where the shard's K'_fu does not fit the budget of one
+static inline bool rows_plan(int64_t N, int M, int d, StreamPlan& p) {
+  p = make_stream_plan(N, M, d);
+  if (p.sc_rows < p.Npad) return false;
+  p.sc_rows = p.Npad;
+  return true;
+}
+// the start of such a pass (Npad > 0), four launches: prologue, R = L^-T as a plain row-major operand, the assembly of all Npad rows,
+// and T_out = K' R (column block c of the upper-triangular R needs k < its end only).  w: carve_wh_rows(ws, p, true).
+void stream_rows_start(const StreamPlan& p, int kid, const KernArgs& ka, const double* X, int64_t ldx, const double* y, const double* Z,
+                       int64_t ldz, int64_t N, int M, const double* kuu_linv, const WhRowsWs& w, double* T_out, hipStream_t st);
 // the fp64 contraction of `nchunks` 16-row chunks of a row-major [rows x Mp] matrix into the per-split slabs (options of the context)
 void launch_syrk(const Ctx& cx, const double* K, int Mp, int64_t nchunks, const SplitMap& smap, int ntiles, int nsplit, int accum,
                  double* slab, hipStream_t st);

@@ -940,6 +940,18 @@ WhRowsWs carve_wh_rows(void* ws, const StreamPlan& p, bool caller_t) {
   return w;
 }
 
+void stream_rows_start(const StreamPlan& p, int kid, const KernArgs& ka, const double* X, int64_t ldx, const double* y, const double* Z,
+                       int64_t ldz, int64_t N, int M, const double* kuu_linv, const WhRowsWs& w, double* T_out, hipStream_t st) {
+  const FwdWs& f = w.f;
+  stream_prologue(p, ka, X, ldx, y, Z, ldz, N, M, f.Xs, f.ys, f.Zs, f.yypart, st);
+  transpose_square(kuu_linv, p.Mp, w.R, st);
+  stream_assemble(p, kid, f.Xs, f.ys, f.Zs, 0, p.Npad, N, M, f.Kfu, f.bpart, st);
+  GemmDesc t;
+  t.A = f.Kfu; t.lda = p.Mp; t.B = w.R; t.ldb = p.Mp; t.C = T_out; t.ldc = p.Mp;
+  t.m = (int)p.Npad; t.n = p.Mp; t.k = p.Mp; t.khi_mask = 2;
+  gemm(t, st);
+}
+
 }  // namespace sgp
 
 using namespace sgp;

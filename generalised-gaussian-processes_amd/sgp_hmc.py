@@ -23,10 +23,11 @@ from .targets import SgpmcTarget
 
 
 class SgpmcModel:
-    """What ``train_sgp_hmc`` returns as ``model``: the target (data, kernel, jitter, engine), the inducing inputs the warm-up left
-    (``Z``, frozen during sampling) and the warm-up's record."""
+    """What ``train_sgp_hmc`` and ``train_sgp_hmc_composite`` return as ``model``: the target (an ``SgpmcTarget`` or a
+    ``CompositeSgpmcTarget``: data, kernel, jitter, engine), the inducing inputs (``Z``, frozen during sampling; the warm-up of
+    ``train_sgp_hmc`` leaves them) and the warm-up's record."""
 
-    def __init__(self, target: SgpmcTarget):
+    def __init__(self, target):
         self.target = target
         self.engine = target.engine
         self.kernel = target.kernel
@@ -39,21 +40,7 @@ class SgpmcModel:
         return self.target.Z
 
 
-class CompositeSgpmcModel:
-    """What ``train_sgp_hmc_composite`` returns as ``model``: the ``CompositeSgpmcTarget`` (data, kernel structure, white / mean
-    switches, jitter, engine) and the frozen inducing inputs."""
-
-    def __init__(self, target: CompositeSgpmcTarget):
-        self.target = target
-        self.engine = target.engine
-        self.kernel = target.kernel
-        self.jitter = target.jitter
-        self.likelihood = target.likelihood
-        self.warmup = {}
-
-    @property
-    def Z(self):
-        return self.target.Z
+CompositeSgpmcModel = SgpmcModel   # the name ``train_sgp_hmc_composite``'s model had while the two were separate classes
 
 
 def _as_tensor(a):
@@ -175,49 +162,56 @@ def predict_sgpmc(model, trace, X_test, n_draws=50):
     a = L^-1 k_u*; y_std = sqrt(var + noise variance).  With a non-Gaussian likelihood ``f_means`` and ``y_stds`` hold the likelihood's
     conditional moments of y per draw (``likelihood_moments``) and ``pred_mean`` their mean over the draws.
 
-    A ``CompositeSgpmcModel`` (``train_sgp_hmc_composite``) is predicted by ``sgpmc_comp_rows`` on X_test without labels, per draw:
+    A model over a ``CompositeSgpmcTarget`` (``train_sgp_hmc_composite``) is predicted by ``sgpmc_comp_rows`` on X_test without labels, per draw:
     mean = a^T v + m(x*), var = kdiag + white - |a|^2."""
-    if isinstance(model, CompositeSgpmcModel):
-        return _predict_composite(model, trace, X_test, n_draws)
     e = model.engine
     Xs = _as_tensor(X_test)
     if Xs.dim() == 1:
         Xs = Xs[:, None]
     Xs = Xs.to(e.device).contiguous()
-    Z = model.Z
-    M = int(Z.shape[0])
     n = min(int(n_draws), len(trace))
     if n <= 0:
         raise ValueError("the trace holds no draws")
-    if model.likelihood == "multiclass":
-        return _predict_multiclass(model, trace, Xs, n)
+    if isinstance(model.target, CompositeSgpmcTarget):
+        per_draw = _predict_composite(model, trace, Xs, n)
+    elif model.likelihood == "multiclass":
+        per_draw = _predict_multiclass(model, trace, Xs, n)
+    else:
+        per_draw = _predict_stationary(model, trace, Xs, n)
+    means, stds = (np.stack(a) for a in zip(*per_draw))
+    return means.mean(0), means, stds
+
+
+def _draw_moments(model, mean, var, s2):
+    """(f_mean, y_std) of one draw from the latent mean and variance: y's own moments under a non-Gaussian likelihood."""
+    if model.likelihood == "gaussian":
+        return mean, np.sqrt(var + s2)
+    return likelihood_moments(model.likelihood, mean, var)
+
+
+def _predict_stationary(model, trace, Xs, n):
+    e, Z = model.engine, model.Z
+    M = int(Z.shape[0])
     LS = torch.zeros(M, M, dtype=torch.float64, device=e.device)
-    f_means, y_stds = [], []
+    out = []
     for i in range(n):
         row = trace[i]
         m = torch.as_tensor(np.asarray(row["V"], dtype=np.float64)).to(e.device).contiguous()
         mean, var, _ = e.svgp_predict(Xs, Z, [float(t) for t in np.asarray(row["lengthscales"]).reshape(-1)], float(row["variance"]), m, LS,
                                       jitter=model.jitter, kernel=model.kernel)
         mean, var = mean.detach().to("cpu").numpy(), np.maximum(var.detach().to("cpu").numpy(), 0.0)
-        if model.likelihood == "gaussian":
-            f_means.append(mean)
-            y_stds.append(np.sqrt(var + float(row["noise_variance"])))
-        else:
-            ym, ys = likelihood_moments(model.likelihood, mean, var)
-            f_means.append(ym)
-            y_stds.append(ys)
-    f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
-    return np.mean(f_means, axis=0), f_means, y_stds
+        out.append(_draw_moments(model, mean, var, float(row["noise_variance"]) if model.likelihood == "gaussian" else None))
+    return out
 
 
 def _predict_multiclass(model, trace, Xs, n):
     """Per draw one ``sgpmc_mc_rows`` call without labels on the test rows (the C latent means and their shared variance), then the class
-    probabilities on the host: ``(pred_mean (T x C), probs (draws x T x C), sqrt(p (1 - p)))``."""
+    probabilities on the host: per draw (probs (T x C), sqrt(p (1 - p)))."""
     e, t = model.engine, model.target
     Z = model.Z
     T, M = int(Xs.shape[0]), int(Z.shape[0])
     t_buf = e.kfu_buffer(T, M)
-    probs = []
+    out = []
     for i in range(n):
         row = trace[i]
         ls, sf2 = [float(v) for v in np.asarray(row["lengthscales"]).reshape(-1)], float(row["variance"])
@@ -225,23 +219,15 @@ def _predict_multiclass(model, trace, Xs, n):
         linv, _ = e.kuu_factor(e.kuu(Z, ls, sf2, model.jitter, model.kernel))
         r = e.sgpmc_mc_rows(Xs, None, Z, ls, sf2, V, linv, t_buf, model.kernel, t.eps)
         mu, var = r["mu"].detach().to("cpu").numpy().T, np.maximum(r["var"].detach().to("cpu").numpy(), sf2 * 2.0 ** -40)
-        probs.append(likelihood_moments("multiclass", mu, var, t.eps)[0])
-    probs = np.stack(probs)
-    return probs.mean(0), probs, np.sqrt(probs * (1.0 - probs))
+        out.append(likelihood_moments("multiclass", mu, var, t.eps))
+    return out
 
 
-def _predict_composite(model, trace, X_test, n_draws):
+def _predict_composite(model, trace, Xs, n):
     e, t = model.engine, model.target
-    Xs = _as_tensor(X_test)
-    if Xs.dim() == 1:
-        Xs = Xs[:, None]
-    Xs = Xs.to(e.device).contiguous()
     Z, M, T = model.Z, int(model.Z.shape[0]), int(Xs.shape[0])
-    n = min(int(n_draws), len(trace))
-    if n <= 0:
-        raise ValueError("the trace holds no draws")
     t_buf = e.kfu_buffer(T, M)
-    f_means, y_stds = [], []
+    out = []
     for i in range(n):
         q = trace[i]["theta_unc"]
         block, white, s2, A, b, _ = t.unpack(q)
@@ -252,15 +238,8 @@ def _predict_composite(model, trace, X_test, n_draws):
         mean, var = r["mu"].detach().to("cpu").numpy(), np.maximum(r["var"].detach().to("cpu").numpy(), 0.0)
         if int(info.item()) != 0:
             raise RuntimeError("K_uu of draw %d is not positive definite (status %d)" % (i, int(info.item())))
-        if model.likelihood == "gaussian":
-            f_means.append(mean)
-            y_stds.append(np.sqrt(var + s2))
-        else:
-            ym, ys = likelihood_moments(model.likelihood, mean, var)
-            f_means.append(ym)
-            y_stds.append(ys)
-    f_means, y_stds = np.vstack(f_means), np.vstack(y_stds)
-    return np.mean(f_means, axis=0), f_means, y_stds
+        out.append(_draw_moments(model, mean, var, s2))
+    return out
 
 
 def get_posterior_predictive_uncertainty_intervals(sample_means, sample_stds):

@@ -342,7 +342,64 @@ def multiclass_labels(y, num_classes=None):
     return C
 
 
-class SgpmcTarget:
+class SgpmcTargetBase:
+    """What the SGPMC targets share outside an evaluation (``SgpmcTarget`` here, ``composite.CompositeSgpmcTarget``): the data intake
+    with the label rules, ``set_Z`` and the caller-owned T.  A target sets ``_NAME`` (its name in the intake's error text) and
+    ``n_theta`` ahead of ``set_Z``.  The evaluations themselves stay with the targets: sharing their envelope through hooks cost
+    2 - 3 us of calls per evaluation, 1 % at the small shapes."""
+
+    LIKELIHOODS = ("gaussian", "bernoulli", "bernoulli_logit", "poisson", "multiclass")
+    n_latent = 1   # latent GPs = columns of whitened inducing values
+
+    def _intake(self, X, y, likelihood, engine):
+        """Sets engine, X (N x d), y (N, on the device, Bernoulli labels as {-1, +1}), likelihood, N, d; returns y on the host."""
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("%s takes the likelihoods %s (got %r)" % (self._NAME, ", ".join(self.LIKELIHOODS), likelihood))
+        if engine is None:
+            from .engine import HipEngine
+            engine = HipEngine(X.device if X.is_cuda else None)
+        self.engine = engine
+        if X.dim() == 1:
+            X = X[:, None]
+        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
+        yh = y.detach().to(dtype=torch.float64, device="cpu").reshape(-1)
+        if self.X.shape[0] != yh.shape[0]:
+            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], yh.shape[0]))
+        if likelihood in ("bernoulli", "bernoulli_logit"):   # {0, 1} or {-1, +1} labels -> {-1, +1}, on the host
+            if not bool(((yh == 0.0) | (yh == 1.0) | (yh == -1.0)).all()) or (bool((yh == 0.0).any()) and bool((yh == -1.0).any())):
+                raise ValueError("Bernoulli labels must be {0, 1} or {-1, +1}")
+            if bool((yh == 0.0).any()):
+                yh = 2.0 * yh - 1.0
+        elif likelihood == "poisson" and not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
+            raise ValueError("Poisson counts must be non-negative integers")
+        self.y = yh.to(engine.device).contiguous()
+        self.likelihood = likelihood
+        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+        self.n_evals = 0
+        self._t_keep = None
+        return yh
+
+    def set_Z(self, Z):
+        if Z.dim() == 1:
+            Z = Z[:, None]
+        Z = Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
+        if Z.shape[1] != self.d:
+            raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
+        self.Z = Z
+        self.M = int(Z.shape[0])
+        self.ndim = self.n_theta + self.M * self.n_latent
+
+    def _t_for(self):
+        e = self.engine
+        if not hasattr(e, "kfu_buffer"):
+            return None
+        need = ((max(self.N, 1) + 255) // 256 * 256) * ((self.M + 127) // 128 * 128)
+        if self._t_keep is None or self._t_keep.numel() < need:
+            self._t_keep = e.kfu_buffer(self.N, self.M)
+        return self._t_keep
+
+
+class SgpmcTarget(SgpmcTargetBase):
     """logp(q) and its gradient for HMC over the hyper-parameters and the whitened inducing values together (GPflow's ``SGPMC``, with a
     Gaussian likelihood models/sgp_hmc.py:38-43), q = [x_var | x_ls (d) | x_noise | v (M)] unconstrained, ndim = d + 2 + M.
 
@@ -375,68 +432,31 @@ class SgpmcTarget:
     ``sgpmc_mc_tail`` -> ``suffstats_bwd_factored(t_in = diag(dv) T - DMU V^T / (2 sf2), y = 0, Cw = -2 I, s2 = 1, bbar = 0)`` ->
     ``kuu_bwd``: ONE pass 2 whatever C is (include/sgp.h, the sgp_sgpmc_mc_rows section), one device-to-host copy."""
 
-    LIKELIHOODS = ("gaussian", "bernoulli", "bernoulli_logit", "poisson", "multiclass")
+    _NAME = "SgpmcTarget"
 
     def __init__(self, X, y, Z, kernel="rbf", jitter=1e-5, engine=None, group=None, likelihood="gaussian", num_classes=None,
                  robustmax_eps=1e-3):
         from .core import _world
-        if likelihood not in self.LIKELIHOODS:
-            raise ValueError("SgpmcTarget takes the likelihoods %s (got %r)" % (", ".join(self.LIKELIHOODS), likelihood))
         if kernel not in ("rbf", "matern32", "matern52"):
             raise ValueError("SgpmcTarget takes the stationary kernels 'rbf', 'matern32', 'matern52' (got %r): composite kernels are "
                              "not supported" % (kernel,))
         if _world(group) > 1:
             raise ValueError("SgpmcTarget runs in one process: a group of %d ranks is not supported" % _world(group))
-        if engine is None:
-            from .engine import HipEngine
-            engine = HipEngine(X.device if X.is_cuda else None)
-        self.engine = engine
-        if X.dim() == 1:
-            X = X[:, None]
-        self.X = X.to(dtype=torch.float64, device=engine.device).contiguous()
-        self.y = y.to(dtype=torch.float64, device=engine.device).reshape(-1).contiguous()
-        if self.X.shape[0] != self.y.shape[0]:
-            raise ValueError("X has %d rows, y has %d" % (self.X.shape[0], self.y.shape[0]))
-        self.likelihood = likelihood
-        if likelihood in ("bernoulli", "bernoulli_logit"):   # {0, 1} or {-1, +1} labels -> {-1, +1}, on the host
-            yh = self.y.detach().to("cpu")
-            if not bool(((yh == 0.0) | (yh == 1.0) | (yh == -1.0)).all()) or (bool((yh == 0.0).any()) and bool((yh == -1.0).any())):
-                raise ValueError("Bernoulli labels must be {0, 1} or {-1, +1}")
-            if bool((yh == 0.0).any()):
-                self.y = (2.0 * yh - 1.0).to(engine.device).contiguous()
-        elif likelihood == "poisson":
-            yh = self.y.detach().to("cpu")
-            if not bool((torch.isfinite(yh) & (yh >= 0.0) & (yh == torch.floor(yh))).all()):
-                raise ValueError("Poisson counts must be non-negative integers")
-        self.n_latent = 1                                     # latent GPs = columns of whitened inducing values
+        yh = self._intake(X, y, likelihood, engine)
         self.eps = float(robustmax_eps)
         if likelihood == "multiclass":
-            self.n_latent = self.num_classes = multiclass_labels(self.y, num_classes)
+            self.n_latent = self.num_classes = multiclass_labels(yh, num_classes)
             if not 0.0 < self.eps < 1.0:
                 raise ValueError("robustmax_eps must lie in (0, 1) (got %r)" % (robustmax_eps,))
         elif num_classes is not None:
             raise ValueError("num_classes belongs to likelihood='multiclass' (got likelihood=%r)" % (likelihood,))
-        self.n_theta = self.X.shape[1] + (2 if likelihood == "gaussian" else 1)   # [x_var | x_ls (d) | x_noise (Gaussian only)]
+        self.n_theta = self.d + (2 if likelihood == "gaussian" else 1)   # [x_var | x_ls (d) | x_noise (Gaussian only)]
         self.kernel = kernel
         self.jitter = float(jitter)
-        self.d = int(self.X.shape[1])
-        self.N = int(self.X.shape[0])
         self._cw_keep = None
         self.whitened_rows_min_work = WHITENED_ROWS_MIN_WORK
         self.last_pass1 = None   # "suffstats_whitened" / "suffstats_whitened_rows": which pass 1 the last evaluation ran
-        self.n_evals = 0
-        self._t_keep = None
         self.set_Z(Z)
-
-    def set_Z(self, Z):
-        if Z.dim() == 1:
-            Z = Z[:, None]
-        Z = Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
-        if Z.shape[1] != self.d:
-            raise ValueError("Z has %d columns, X has %d" % (Z.shape[1], self.d))
-        self.Z = Z
-        self.M = int(Z.shape[0])
-        self.ndim = self.n_theta + self.M * self.n_latent
 
     def start(self):
         """GPflow's defaults as the reference sets them (models/sgp_hmc.py:36): variance log(2)^2, lengthscales log 2, likelihood
@@ -456,15 +476,6 @@ class SgpmcTarget:
         if self.likelihood == "multiclass":
             c["V"] = c["V"].reshape(self.num_classes, self.M)   # class-major
         return c
-
-    def _t_for(self):
-        e = self.engine
-        if not hasattr(e, "kfu_buffer"):
-            return None
-        need = ((max(self.N, 1) + 255) // 256 * 256) * ((self.M + 127) // 128 * 128)
-        if self._t_keep is None or self._t_keep.numel() < need:
-            self._t_keep = e.kfu_buffer(self.N, self.M)
-        return self._t_keep
 
     def _cw(self):
         """-2 I (M x M): the whitened core that turns the factored pass 2 into the N-side gradient of a non-conjugate likelihood."""
