@@ -16,7 +16,10 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
   * ``--holdout K`` (0 by default): K more points per data set, kept out of the fit and the sampling: the held-out NLPD and RMSE of the
     ML-II plug-in (``Ml2Result.predict``) and, with ``--hmc``, of the mixture over the draws (``ExactNutsResult.predict``) -- whether
     sampling theta predicts better than plugging in its ML-II value (summary keys ``<sweep>_ml2_nlpd``, ``_hmc_nlpd``, ``_ml2_rmse``,
-    ``_hmc_rmse``, one entry per cell).
+    ``_hmc_rmse``, one entry per cell);
+  * ``--sparse M`` (0 by default): the sparse ML-II estimates beside the exact ones -- the collapsed bound with M inducing inputs
+    (``ggp_amd.fit_sgpr_batch``, ``learn_Z=True``: Adam for ``--sparse_steps`` steps, all data sets of a cell in lock step with one
+    launch per step), started at M evenly spaced training inputs; recorded as ``<sweep>_sparse_ls``, ``_sf``, ``_sn``, ``_elbo``.
 
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
@@ -36,15 +39,19 @@ TRUE = {"sig_sd": 5.0, "lengthscale": 2.0, "noise_sd": 1.0}
 AMP_BOUNDS = (1e-5, 1e5)
 
 
-def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None, holdout=0):
+def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None, holdout=0, sparse=None):
     """cells: [(label, n_train, noise variance)].  Fits every cell with the noise fixed at its true variance and with the noise learnt.
     Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data.  ``hmc`` = dict(chains, tune, draws): also
     res["hmc"] = dict(log_ls, log_sf, log_sn: len(cells) x n_sets posterior means, diverging: the cell's share of diverging draws).
     ``holdout`` = K > 0: K more points are drawn per cell and kept out of the fit and the sampling; res["learn"] (the ML-II plug-in,
-    ``Ml2Result.predict``) and res["hmc"] (the mixture over the draws, ``ExactNutsResult.predict``) gain nlpd, rmse: len(cells) x n_sets."""
+    ``Ml2Result.predict``) and res["hmc"] (the mixture over the draws, ``ExactNutsResult.predict``) gain nlpd, rmse: len(cells) x n_sets.
+    ``sparse`` = dict(M, steps): also res["sparse"] = dict(ls, sf, sn, elbo: len(cells) x n_sets, seconds), the optimum of the collapsed
+    bound with min(M, n) inducing inputs (it draws nothing from ``rng``)."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
     if hmc:
         res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
+    if sparse:
+        res["sparse"] = {"ls": [], "sf": [], "sn": [], "elbo": [], "seconds": []}
     if holdout:
         for m in ("learn", "hmc") if hmc else ("learn",):
             res[m].update(nlpd=[], rmse=[])
@@ -64,6 +71,14 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             if holdout and mode == "learn":
                 pred = fit.predict(X_test, Y_test)
                 r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
+        if sparse:
+            t0 = time.time()
+            Xs = np.sort(X, 0)
+            Z0 = Xs[np.round(np.linspace(0, n - 1, min(sparse["M"], n))).astype(int)]
+            fit = ggp_amd.fit_sgpr_batch(X, Y, Z0, max_steps=sparse["steps"], learn_Z=True, seed=seed, engine=engine)
+            r = res["sparse"]
+            r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
+            r["elbo"].append(fit.elbo), r["seconds"].append(time.time() - t0)
         if hmc:
             post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
             mean, r = post.posterior_mean(), res["hmc"]
@@ -76,14 +91,14 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
 
 
 def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n_sets=100, grid=50, n_noise=30, bimodal=False, seed=57,
-        engine=None, hmc=None, holdout=0):
+        engine=None, hmc=None, holdout=0, sparse=None):
     rng = np.random.default_rng(seed)
     out, summary = {}, {"sizes": list(sizes), "noise_vars": list(noise_vars), "n_sets": n_sets, "true": TRUE}
     t0 = time.time()
     size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed, hmc,
-                                        holdout)
+                                        holdout, sparse)
     noise_res, noise_data, latent = sweep([(v, n_noise, float(v)) for v in noise_vars], n_sets, 1e4, 5, rng, latent, not bimodal, engine,
-                                          seed, hmc, holdout)
+                                          seed, hmc, holdout, sparse)
     summary["fit_seconds"] = time.time() - t0
     for name, res in (("size", size_res), ("noise", noise_res)):
         for mode, r in res.items():
@@ -96,6 +111,10 @@ def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n
                 for k in ("log_ls", "log_sf", "log_sn"):
                     summary["%s_hmc_mean_%s" % (name, k)] = r[k].mean(1).tolist()
                 summary["%s_hmc_diverging" % name], summary["%s_hmc_seconds" % name] = r["diverging"].tolist(), r["seconds"].tolist()
+                continue
+            if mode == "sparse":  # beside ML-II's log of the mean fitted lengthscale: the same figure of the sparse optimum
+                summary["%s_sparse_mean_log_ls" % name] = np.log(np.nanmean(r["ls"], 1)).tolist()
+                summary["%s_sparse_seconds" % name] = r["seconds"].tolist()
                 continue
             summary["%s_%s_mean_log_ls" % (name, mode)] = np.log(r["ls"].mean(1)).tolist()
             summary["%s_%s_batched_evaluations" % (name, mode)] = r["n_batches"].tolist()
@@ -155,10 +174,12 @@ def main(argv=None, engine=None):
     ap.add_argument("--hmc_tune", type=int, default=500)
     ap.add_argument("--hmc_draws", type=int, default=500)
     ap.add_argument("--holdout", type=int, default=0, help="points per data set kept out of the fit and the sampling, and predicted")
+    ap.add_argument("--sparse", type=int, default=0, help="also fit the collapsed sparse bound with this many inducing inputs (at most 64)")
+    ap.add_argument("--sparse_steps", type=int, default=2000)
     args = ap.parse_args(argv)
     hmc = {"chains": args.hmc_chains, "tune": args.hmc_tune, "draws": args.hmc_draws} if args.hmc else None
     out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine, hmc=hmc,
-                       holdout=args.holdout)
+                       holdout=args.holdout, sparse={"M": args.sparse, "steps": args.sparse_steps} if args.sparse else None)
     os.makedirs(args.out, exist_ok=True)
     base = os.path.join(args.out, "hyperparameter_identification")
     np.savez_compressed(base + ".npz", **out)

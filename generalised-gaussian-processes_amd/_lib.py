@@ -268,9 +268,22 @@ EXACT_PREDICT_PROTOTYPES = {
     "sgp_exact_mixture_reduce": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# the companion library libsgp_vfe_batch_hip.so (include/sgp_vfe_batch.h): P collapsed sparse-GP bounds with their gradients in one launch
+_VB_BATCH = [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _vp,
+             _sz, _vp]
+VFE_BATCH_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_vfe_batch_hip.so")
+VFE_BATCH_PROTOTYPES = {
+    "sgp_vfe_batch_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "sgp_vfe_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_vfe_eval_batch": (_i32, _VB_BATCH),
+    "sgp_ctx_vfe_eval_batch": (_i32, [_vp] + _VB_BATCH),
+}
+VFE_BATCH_MAX_M, VFE_BATCH_MAX_N, VFE_BATCH_MAX_D, VFE_BATCH_MAX_P = 64, 65536, 8, 2 ** 24 - 1  # the limits of sgp_vfe_eval_batch
+
 _LIB = None
 _EXACT_NUTS_LIB = None
 _EXACT_PREDICT_LIB = None
+_VFE_BATCH_LIB = None
 
 
 def load_library(path: str | None = None):
@@ -333,6 +346,14 @@ def load_exact_predict_library():
     if _EXACT_PREDICT_LIB is None:
         _EXACT_PREDICT_LIB = _load_companion(EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES)
     return _EXACT_PREDICT_LIB
+
+
+def load_vfe_batch_library():
+    """The same for the batched collapsed bound's library (include/sgp_vfe_batch.h)."""
+    global _VFE_BATCH_LIB
+    if _VFE_BATCH_LIB is None:
+        _VFE_BATCH_LIB = _load_companion(VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES)
+    return _VFE_BATCH_LIB
 
 
 def check(fn_name: str, status: int):

@@ -1001,6 +1001,44 @@ class HipEngine:
         return out[:, 0], out, grads, info
 
     @property
+    def vfe_batch_lib(self):
+        """The companion library of the batched collapsed bound (include/sgp_vfe_batch.h), loaded on first use."""
+        return _lib.load_vfe_batch_library()
+
+    def vfe_eval_batch(self, X, Y, Z, theta, ix=None, iy=None, iz=None, kernel="rbf", jitter=1e-6, want_grad=True, want_gz=False):
+        """P collapsed (VFE) bounds with their gradients in ONE launch, one workgroup per problem (include/sgp_vfe_batch.h:
+        sgp_vfe_eval_batch).  X: nX x N x d (or N x d), Y: nY x N (or N), Z: nZ x M x d (or M x d), theta: P x (d + 2) rows [ls_1..d |
+        sf2 | s2] -- device tensors; problem p takes data set ix[p], target iy[p] and inducing set iz[p] (None: set 0).  Returns device
+        tensors (out [P, d + 5] = [F | dF/dls | dF/dsf2 | dF/ds2 | logmarg | trace], g_Z [P, M, d] or None, info [P] int32); nothing is
+        synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        Z = Z if Z.dim() == 3 else Z[None]
+        nX, N, d = X.shape
+        nY, (nZ, M) = Y.shape[0], Z.shape[:2]
+        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z"), self._chk(theta, "theta")
+        if Y.shape[1] != N or Z.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
+            raise ValueError("shapes: X %s, Y %s, Z %s, theta %s (expected theta P x %d)"
+                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(theta.shape), d + 2))
+        P = theta.shape[0]
+        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
+                and 1 <= P <= _lib.VFE_BATCH_MAX_P):
+            raise ValueError("vfe_eval_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d and 1 <= P < 2^24 (got M %d, N %d, d %d, P %d)"
+                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, M, N, d, P))
+        ix, iy, iz = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy"), self._set_index(iz, nZ, P, "iz")
+        out = self.empty(P, d + 5)
+        gz = self.empty(P, M, d) if want_grad and want_gz else None
+        info = torch.empty(P, dtype=torch.int32, device=self.device)
+        lib = self.vfe_batch_lib
+        ws = self._workspace("vfe_batch", lib.sgp_vfe_batch_workspace_bytes(P, N, M, d, 1 if want_grad else 0, 1 if gz is not None else 0))
+        st = lib.sgp_ctx_vfe_eval_batch(
+            self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), self._ptr(Z), M * d, d, self._ptr(iz),
+            self._ptr(theta), P, N, M, d, _kernel_id(kernel), float(jitter), 1 if want_grad else 0, self._ptr(out), self._ptr(gz),
+            self._ptr(info), self._ptr(ws), ws.numel(), self._stream())
+        _lib.check("sgp_vfe_eval_batch", st)
+        return out, gz, info
+
+    @property
     def exact_predict_lib(self):
         """The companion library of the batched predictive (include/sgp_exact_predict.h), loaded on first use."""
         return _lib.load_exact_predict_library()
