@@ -280,10 +280,14 @@ VFE_BATCH_PROTOTYPES = {
 }
 VFE_BATCH_MAX_M, VFE_BATCH_MAX_N, VFE_BATCH_MAX_D, VFE_BATCH_MAX_P = 64, 65536, 8, 2 ** 24 - 1  # the limits of sgp_vfe_eval_batch
 
+# key -> (path, prototypes) of a companion library; _COMPANION_LIBS caches what has been loaded
+_COMPANION_TABLE = {
+    "exact_nuts": (EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES),
+    "exact_predict": (EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES),
+    "vfe_batch": (VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES),
+}
 _LIB = None
-_EXACT_NUTS_LIB = None
-_EXACT_PREDICT_LIB = None
-_VFE_BATCH_LIB = None
+_COMPANION_LIBS = {}
 
 
 def load_library(path: str | None = None):
@@ -314,7 +318,11 @@ def load_library(path: str | None = None):
     return lib
 
 
-def _load_companion(p, prototypes):
+def _load_companion(key):
+    """dlopen a companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
+    if key in _COMPANION_LIBS:
+        return _COMPANION_LIBS[key]
+    p, prototypes = _COMPANION_TABLE[key]
     load_library()
     if not os.path.exists(p):
         raise SgpLibraryError("%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % p)
@@ -329,31 +337,23 @@ def _load_companion(p, prototypes):
             raise SgpLibraryError("%s does not export %s" % (p, name)) from e
         fn.restype = res
         fn.argtypes = args
+    _COMPANION_LIBS[key] = lib
     return lib
 
 
 def load_exact_nuts_library():
-    """dlopen the companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
-    global _EXACT_NUTS_LIB
-    if _EXACT_NUTS_LIB is None:
-        _EXACT_NUTS_LIB = _load_companion(EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES)
-    return _EXACT_NUTS_LIB
+    """The batched sampler's library (include/sgp_exact_nuts.h)."""
+    return _load_companion("exact_nuts")
 
 
 def load_exact_predict_library():
-    """The same for the batched predictive's library (include/sgp_exact_predict.h)."""
-    global _EXACT_PREDICT_LIB
-    if _EXACT_PREDICT_LIB is None:
-        _EXACT_PREDICT_LIB = _load_companion(EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES)
-    return _EXACT_PREDICT_LIB
+    """The batched predictive's library (include/sgp_exact_predict.h)."""
+    return _load_companion("exact_predict")
 
 
 def load_vfe_batch_library():
-    """The same for the batched collapsed bound's library (include/sgp_vfe_batch.h)."""
-    global _VFE_BATCH_LIB
-    if _VFE_BATCH_LIB is None:
-        _VFE_BATCH_LIB = _load_companion(VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES)
-    return _VFE_BATCH_LIB
+    """The batched collapsed bound's library (include/sgp_vfe_batch.h)."""
+    return _load_companion("vfe_batch")
 
 
 def check(fn_name: str, status: int):

@@ -19,12 +19,9 @@ SOURCES = ["sgp_ctx.hip", "sgp_suffstats_fwd.hip", "sgp_suffstats_i8.hip", "sgp_
 VERSION_SCRIPT = "libsgp.map"
 # Companion libraries: (library, sources, public header).  Each is one more shared object beside libsgp_hip.so with a C header of its
 # own, linked to the core library; the core's surface (include/sgp.h) does not grow with them.
-COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h")]
-# Companions added after the sampler's.  COMPANIONS is held to exactly the sampler's entry by that library's ABI test, so later
-# libraries are listed here; build_companions walks all the lists with the same rule.
-MORE_COMPANIONS = [("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h")]
-# ... and MORE_COMPANIONS to exactly the predictive's entry by its own: companions of the sparse models go to a third list.
-SPARSE_COMPANIONS = [("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
+COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h"),
+              ("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h"),
+              ("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
 PUBLIC_HEADER = os.path.join("..", "..", "include", "sgp.h")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # only the SGP_API symbols of include/sgp.h leave the library
 
@@ -66,7 +63,7 @@ def _companion_digest(core_digest: str, sources, header) -> str:
 def build_companions(force: bool = False, verbose: bool = False):
     """Compile and link every companion library (after the core library, which they link to).  Returns their paths."""
     hipcc, core, paths = None, _digest(), []
-    for name, sources, header in COMPANIONS + MORE_COMPANIONS + SPARSE_COMPANIONS:
+    for name, sources, header in COMPANIONS:
         path = os.path.join(CSRC, name)
         stamp, digest = path + ".sha256", _companion_digest(core, sources, header)
         paths.append(path)

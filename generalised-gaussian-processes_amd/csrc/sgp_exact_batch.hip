@@ -21,26 +21,6 @@ __global__ __launch_bounds__(256) void exact_batch_kernel(const double* __restri
   eb_eval<KID, NP>(sh, theta + p * (d + 2), N, d, with_grad, out + p * 4, grads + p * (d + 2), info + p);
 }
 
-template <int KID>
-static void launch_eb(int NP, int64_t P, hipStream_t st, const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride,
-                      const int* ix, const int* iy, const double* theta, int N, int d, int with_grad, double* out, double* grads,
-                      int* info) {
-  const dim3 grid((unsigned)P);
-  if (NP == 32) exact_batch_kernel<KID, 32><<<grid, 256, 0, st>>>(X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, with_grad, out, grads, info);
-  else if (NP == 64) exact_batch_kernel<KID, 64><<<grid, 256, 0, st>>>(X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, with_grad, out, grads, info);
-  else exact_batch_kernel<KID, 128><<<grid, 256, 0, st>>>(X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, with_grad, out, grads, info);
-}
-
-template <int KID>
-static int occupancy_eb(int NP) {
-  int n = 0;
-  hipError_t e;
-  if (NP == 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_batch_kernel<KID, 32>, 256, 0);
-  else if (NP == 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_batch_kernel<KID, 64>, 256, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_batch_kernel<KID, 128>, 256, 0);
-  return e == hipSuccess ? n : SGP_ERR_LAUNCH;
-}
-
 }  // namespace sgp
 
 using namespace sgp;
@@ -52,22 +32,17 @@ static int exact_batch_check(int64_t P, int N, int d, int kernel_id) {
   return SGP_OK;
 }
 
-// The kernel keeps everything in LDS; the one aligned unit it reports keeps "0 = unsupported shape" of the other workspace queries.
 extern "C" size_t sgp_exact_batch_workspace_bytes(int64_t P, int N, int d, int with_grad) {
   (void)with_grad;
-  return exact_batch_check(P, N, d, 0) == SGP_OK ? 256 : 0;
+  return exact_batch_check(P, N, d, 0) == SGP_OK ? WG_WS_UNIT : 0;
 }
 
 // Workgroups of N's size class that one CU holds at a time, as the runtime counts them (registers and LDS of the loaded code object).
 extern "C" int sgp_exact_batch_occupancy(int N, int kernel_id) {
   const int chk = exact_batch_check(1, N, 1, kernel_id);
   if (chk != SGP_OK) return chk;
-  const int NP = eb_size_class(N);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: return occupancy_eb<SGP_KERNEL_RBF>(NP);
-    case SGP_KERNEL_MATERN32: return occupancy_eb<SGP_KERNEL_MATERN32>(NP);
-    default: return occupancy_eb<SGP_KERNEL_MATERN52>(NP);
-  }
+  return with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N),
+                                     [](auto kid, auto np) { return wg_occupancy(exact_batch_kernel<kid(), np()>); });
 }
 
 extern "C" int sgp_exact_eval_batch(const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride, const int* ix,
@@ -77,13 +52,9 @@ extern "C" int sgp_exact_eval_batch(const double* X, int64_t x_stride, int64_t l
   if (chk != SGP_OK) return chk;
   if (!X || !Y || !theta || !out || !info || (with_grad && !grads) || ldx < d || x_stride < 0 || y_stride < 0) return SGP_ERR_ARG;
   if (!ws || ws_bytes < sgp_exact_batch_workspace_bytes(P, N, d, with_grad)) return SGP_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int NP = eb_size_class(N);
-  const int wg = with_grad ? 1 : 0;
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: launch_eb<SGP_KERNEL_RBF>(NP, P, st, X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, wg, out, grads, info); break;
-    case SGP_KERNEL_MATERN32: launch_eb<SGP_KERNEL_MATERN32>(NP, P, st, X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, wg, out, grads, info); break;
-    default: launch_eb<SGP_KERNEL_MATERN52>(NP, P, st, X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d, wg, out, grads, info); break;
-  }
+  with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N), [&](auto kid, auto np) {
+    exact_batch_kernel<kid(), np()><<<dim3((unsigned)P), 256, 0, (hipStream_t)stream>>>(X, x_stride, ldx, Y, y_stride, ix, iy, theta, N, d,
+                                                                                       with_grad ? 1 : 0, out, grads, info);
+  });
   return check_launch();
 }

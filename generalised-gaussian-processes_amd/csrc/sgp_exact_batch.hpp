@@ -9,18 +9,12 @@
 //   dF/dls_q = 1/2 sum G dA/dls_q ; dF/dsf2 = 1/2 sum G k' ; dF/ds2 = 1/2 (alpha.alpha - tr A^-1)              (sgp_exact_eval's convention)
 //
 // The LDS image M is Nr x Nr (Nr = N rounded up to 16, identity in the padding) inside NP x (NP + 2) doubles, NP in {32, 64, 128} the
-// size class.  Row stride NP + 2 = 2 (mod 32) eight-byte slots:
-//   * "16 rows x 4 consecutive columns" (MFMA operands whose contraction index runs along a row: the rank-16 trailing update, the Inv
-//     operand of the triangular inversion) -- a 32-lane group touches slots 2 r + c, r < 16, c < 2: all distinct;
-//   * "4 rows x 16 consecutive columns" (contraction index running down a column: the A^-1 tiles, the dominant N^3 / 3 phase) -- the
-//     four lane groups of an MFMA take the rows k0 + {0, 8, 4, 12} + s instead of k0 + 4 s + {0, 1, 2, 3}, so the two rows of a
-//     32-lane group are 8 apart = 16 slots: all distinct.  (Any fixed assignment of the 16 rows to the 16 (group, step) pairs is the
-//     same sum in another, still fixed, order.)
-//   * row reads (assembly, alpha) are contiguous; the thread-per-row panel solves and the accumulator-tile loads and stores (two
-//     adjacent rows per lane group) are 2-way -- 32 eight-byte accesses per thread and panel, off the MFMA phases.
-// Every sum has a fixed order and depends on nothing outside the problem: the same bits on every call, stream and batch.
+// size class: the layout of sgp_wg_dense.hpp (row stride, the two MFMA operand patterns, the row permutation `kperm` of eb_eval).  Row
+// reads (assembly, alpha) are contiguous.  Every sum has a fixed order and depends on nothing outside the problem: the same bits on
+// every call, stream and batch.
 #pragma once
 #include "sgp_common.hpp"
+#include "sgp_wg_dense.hpp"
 
 namespace sgp {
 
@@ -339,7 +333,7 @@ __device__ __forceinline__ void eb_eval(EbShared<NP>& sh, const double* __restri
 #pragma unroll
   for (int q = 0; q < EB_MAXD; ++q) sq[q] = 0.0;
   double sk = 0.0;
-  const int kperm = 8 * (l4 & 1) + 4 * (l4 >> 1);  // see the head of the file
+  const int kperm = 8 * (l4 & 1) + 4 * (l4 >> 1);  // see the head of sgp_wg_dense.hpp
   for (int t = wave; t < nb * (nb + 1) / 2; t += 4) {
     int bi, bj;
     eb_tri(t, bi, bj);

@@ -27,7 +27,7 @@ constexpr int EN_ND = EB_MAXD + 2;
 constexpr int EN_MAX_TREEDEPTH = NUTS_MAXDEPTH - 1;
 constexpr int64_t EN_MAXC = EB_MAXP;  // one workgroup per chain; C x 19 kB of workspace and C x n_draws x (d + 2) sample indices stay far inside 64 bits
 constexpr int EN_BAD_START = 1;       // info: the start position has no finite density
-constexpr size_t EN_WS_HEAD = 256;    // the finished-chains counter, alone in its aligned unit
+constexpr size_t EN_WS_HEAD = WG_WS_UNIT;  // the finished-chains counter, alone in its aligned unit
 constexpr int EN_LDS_PER_CU = 163840;
 enum { EN_EVAL = 1, EN_SKIP, EN_STOP, EN_DONE, EN_BAD };
 
@@ -218,24 +218,6 @@ __global__ __launch_bounds__(256, (NP <= 64 ? 2 : 1)) void exact_nuts_kernel(EnA
   }
 }
 
-template <int KID>
-static void launch_en(int NP, int64_t C, hipStream_t st, const EnArgs& a) {
-  const dim3 grid((unsigned)C);
-  if (NP == 32) exact_nuts_kernel<KID, 32><<<grid, 256, 0, st>>>(a);
-  else if (NP == 64) exact_nuts_kernel<KID, 64><<<grid, 256, 0, st>>>(a);
-  else exact_nuts_kernel<KID, 128><<<grid, 256, 0, st>>>(a);
-}
-
-template <int KID>
-static int occupancy_en(int NP) {
-  int n = 0;
-  hipError_t e;
-  if (NP == 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_nuts_kernel<KID, 32>, 256, 0);
-  else if (NP == 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_nuts_kernel<KID, 64>, 256, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_nuts_kernel<KID, 128>, 256, 0);
-  return e == hipSuccess ? n : SGP_ERR_LAUNCH;
-}
-
 }  // namespace sgp
 
 using namespace sgp;
@@ -255,12 +237,8 @@ extern "C" size_t sgp_exact_nuts_batch_workspace_bytes(int64_t C, int N, int d) 
 extern "C" int sgp_exact_nuts_batch_occupancy(int N, int kernel_id) {
   const int chk = exact_nuts_check(1, N, 1, kernel_id);
   if (chk != SGP_OK) return chk;
-  const int NP = eb_size_class(N);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: return occupancy_en<SGP_KERNEL_RBF>(NP);
-    case SGP_KERNEL_MATERN32: return occupancy_en<SGP_KERNEL_MATERN32>(NP);
-    default: return occupancy_en<SGP_KERNEL_MATERN52>(NP);
-  }
+  return with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N),
+                                     [](auto kid, auto np) { return wg_occupancy(exact_nuts_kernel<kid(), np()>); });
 }
 
 static EnArgs en_args(double* samples, double* stats, double* seconds, int64_t* evaluations, int64_t* draws, int* info, void* ws) {
@@ -308,12 +286,9 @@ extern "C" int sgp_exact_nuts_batch_advance(const double* X, int64_t x_stride, i
   EnArgs a = en_args(samples, stats, seconds, evaluations, draws, info, ws);
   a.X = X, a.x_stride = x_stride, a.ldx = ldx, a.Y = Y, a.y_stride = y_stride, a.ix = ix, a.iy = iy;
   a.N = N, a.d = d, a.jitter = jitter, a.evals_per_launch = evals_per_launch;
-  const int NP = eb_size_class(N);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: launch_en<SGP_KERNEL_RBF>(NP, C, st, a); break;
-    case SGP_KERNEL_MATERN32: launch_en<SGP_KERNEL_MATERN32>(NP, C, st, a); break;
-    default: launch_en<SGP_KERNEL_MATERN52>(NP, C, st, a); break;
-  }
+  with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N), [&](auto kid, auto np) {
+    exact_nuts_kernel<kid(), np()><<<dim3((unsigned)C), 256, 0, st>>>(a);
+  });
   if (check_launch() != SGP_OK) return SGP_ERR_LAUNCH;
   unsigned long long done = 0;  // the one read-back of a launch: how many chains have finished
   if (hipMemcpyAsync(&done, a.finished, sizeof(done), hipMemcpyDeviceToHost, st) != hipSuccess) return SGP_ERR_LAUNCH;
@@ -322,18 +297,11 @@ extern "C" int sgp_exact_nuts_batch_advance(const double* X, int64_t x_stride, i
   return SGP_OK;
 }
 
-// The context twins: the sampler reads no context option, so what a context means here is the device it belongs to.
-static bool exact_nuts_ctx_on_current_device(const sgp_ctx* ctx) {
-  if (!ctx) return true;  // the default context follows the caller
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return true;  // no device at all: the argument checks and the launch report that
-  return dev == sgp_ctx_device(ctx);
-}
 extern "C" int sgp_ctx_exact_nuts_batch_begin(sgp_ctx* ctx, const double* q0, const uint64_t* seed, int64_t C, int N, int d, int kernel_id,
                                               int n_tune, int n_draws, int max_treedepth, double step_scale, double target_accept,
                                               double* samples, double* stats, double* seconds, int64_t* evaluations, int64_t* draws,
                                               int* info, void* ws, size_t ws_bytes, sgp_stream_t stream) {
-  if (!exact_nuts_ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  if (!ctx_device_matches(ctx)) return SGP_ERR_ARG;
   return sgp_exact_nuts_batch_begin(q0, seed, C, N, d, kernel_id, n_tune, n_draws, max_treedepth, step_scale, target_accept, samples, stats,
                                     seconds, evaluations, draws, info, ws, ws_bytes, stream);
 }
@@ -342,7 +310,7 @@ extern "C" int sgp_ctx_exact_nuts_batch_advance(sgp_ctx* ctx, const double* X, i
                                                 double jitter, double* samples, double* stats, double* seconds, int64_t* evaluations,
                                                 int64_t* draws, int* info, int evals_per_launch, int64_t* finished, void* ws,
                                                 size_t ws_bytes, sgp_stream_t stream) {
-  if (!exact_nuts_ctx_on_current_device(ctx)) return SGP_ERR_ARG;
+  if (!ctx_device_matches(ctx)) return SGP_ERR_ARG;
   return sgp_exact_nuts_batch_advance(X, x_stride, ldx, Y, y_stride, ix, iy, C, N, d, kernel_id, jitter, samples, stats, seconds,
                                       evaluations, draws, info, evals_per_launch, finished, ws, ws_bytes, stream);
 }

@@ -12,7 +12,7 @@
 // four waves' words are added in a fixed order.
 //
 // The K* tile lies TRANSPOSED in LDS, ks[t][k] with the row stride NP + 2 of the image: in V = L^-1 K* it is the B operand, whose
-// contraction index k then runs along a row -- the "16 rows x 4 consecutive columns" pattern of sgp_exact_batch.hpp, slots 2 t + c
+// contraction index k then runs along a row -- the "16 rows x 4 consecutive columns" pattern of sgp_wg_dense.hpp, slots 2 t + c
 // (mod 32) of a 32-lane group all distinct, the same as the A operand's read of L^-1.  Stored as k x 16 the operand would be "4 rows x
 // 16 consecutive columns", which no stride below 32 separates without permuting the rows of a 16-block (stride 17: one 2-way conflict
 // per read; the image's row permutation needs 16 slots between rows 8 apart, which 17 does not give).  The transposed tile is also the
@@ -137,24 +137,6 @@ __global__ __launch_bounds__(256) void exact_predict_kernel(EpArgs a) {
   if (tid == 0) a.info[p] = 0;
 }
 
-template <int KID>
-static void launch_ep(int NP, int64_t P, hipStream_t st, const EpArgs& a) {
-  const dim3 grid((unsigned)P);
-  if (NP == 32) exact_predict_kernel<KID, 32><<<grid, 256, 0, st>>>(a);
-  else if (NP == 64) exact_predict_kernel<KID, 64><<<grid, 256, 0, st>>>(a);
-  else exact_predict_kernel<KID, 128><<<grid, 256, 0, st>>>(a);
-}
-
-template <int KID>
-static int occupancy_ep(int NP) {
-  int n = 0;
-  hipError_t e;
-  if (NP == 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_predict_kernel<KID, 32>, 256, 0);
-  else if (NP == 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_predict_kernel<KID, 64>, 256, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, exact_predict_kernel<KID, 128>, 256, 0);
-  return e == hipSuccess ? n : SGP_ERR_LAUNCH;
-}
-
 // Work item = (group, chunk of 256 test points); the items are dealt to the workgroups in a fixed stride.  Nothing is summed across
 // threads, so how the items are dealt changes no bit.
 __global__ __launch_bounds__(256) void exact_mixture_kernel(const double* __restrict__ mean, const double* __restrict__ var,
@@ -192,21 +174,16 @@ static int exact_predict_check(int64_t P, int N, int d, int64_t T, int kernel_id
   return SGP_OK;
 }
 
-// The kernel keeps everything in LDS; the one aligned unit it reports keeps "0 = unsupported shape" of the other workspace queries.
 extern "C" size_t sgp_exact_predict_batch_workspace_bytes(int64_t P, int N, int d, int64_t T) {
-  return exact_predict_check(P, N, d, T, 0) == SGP_OK ? 256 : 0;
+  return exact_predict_check(P, N, d, T, 0) == SGP_OK ? WG_WS_UNIT : 0;
 }
 
 // Workgroups of N's size class that one CU holds at a time, as the runtime counts them (registers and LDS of the loaded code object).
 extern "C" int sgp_exact_predict_batch_occupancy(int N, int kernel_id) {
   const int chk = exact_predict_check(1, N, 1, 1, kernel_id);
   if (chk != SGP_OK) return chk;
-  const int NP = eb_size_class(N);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: return occupancy_ep<SGP_KERNEL_RBF>(NP);
-    case SGP_KERNEL_MATERN32: return occupancy_ep<SGP_KERNEL_MATERN32>(NP);
-    default: return occupancy_ep<SGP_KERNEL_MATERN52>(NP);
-  }
+  return with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N),
+                                     [](auto kid, auto np) { return wg_occupancy(exact_predict_kernel<kid(), np()>); });
 }
 
 extern "C" int sgp_exact_predict_batch(const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride, const double* Xs,
@@ -225,25 +202,17 @@ extern "C" int sgp_exact_predict_batch(const double* X, int64_t x_stride, int64_
   a.ix = ix, a.iy = iy, a.ixs = ixs;
   a.T = (int)T, a.N = N, a.d = d, a.pred_noise = pred_noise ? 1 : 0;
   a.mean = mean, a.var = var, a.info = info;
-  hipStream_t st = (hipStream_t)stream;
-  const int NP = eb_size_class(N);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: launch_ep<SGP_KERNEL_RBF>(NP, P, st, a); break;
-    case SGP_KERNEL_MATERN32: launch_ep<SGP_KERNEL_MATERN32>(NP, P, st, a); break;
-    default: launch_ep<SGP_KERNEL_MATERN52>(NP, P, st, a); break;
-  }
+  with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N), [&](auto kid, auto np) {
+    exact_predict_kernel<kid(), np()><<<dim3((unsigned)P), 256, 0, (hipStream_t)stream>>>(a);
+  });
   return check_launch();
 }
 
-// The context twin: the kernel reads no context option, so what a context means here is the device it belongs to.
 extern "C" int sgp_ctx_exact_predict_batch(sgp_ctx* ctx, const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride,
                                            const double* Xs, int64_t xs_stride, int64_t ldxs, int64_t T, const int* ix, const int* iy,
                                            const int* ixs, const double* theta, int64_t P, int N, int d, int kernel_id, int pred_noise,
                                            double* mean, double* var, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream) {
-  if (ctx) {  // (NULL: the default context follows the caller)
-    int dev = -1;
-    if (hipGetDevice(&dev) == hipSuccess && dev != sgp_ctx_device(ctx)) return SGP_ERR_ARG;
-  }
+  if (!ctx_device_matches(ctx)) return SGP_ERR_ARG;
   return sgp_exact_predict_batch(X, x_stride, ldx, Y, y_stride, Xs, xs_stride, ldxs, T, ix, iy, ixs, theta, P, N, d, kernel_id, pred_noise,
                                  mean, var, info, ws, ws_bytes, stream);
 }
@@ -254,7 +223,7 @@ static int exact_mixture_check(int64_t G, int64_t T) {
   return SGP_OK;
 }
 
-extern "C" size_t sgp_exact_mixture_workspace_bytes(int64_t G, int64_t T) { return exact_mixture_check(G, T) == SGP_OK ? 256 : 0; }
+extern "C" size_t sgp_exact_mixture_workspace_bytes(int64_t G, int64_t T) { return exact_mixture_check(G, T) == SGP_OK ? WG_WS_UNIT : 0; }
 
 extern "C" int sgp_exact_mixture_reduce(const double* mean, const double* var, const int* info, const int64_t* offsets, int64_t G, int64_t T,
                                         const double* Ytest, double* mix_mean, double* mix_var, double* logpdf, double* mean_logpdf,

@@ -20,24 +20,6 @@ __global__ __launch_bounds__(256, SGP_VB_MIN_WAVES(MP)) void vfe_batch_kernel(Vb
   vb_eval<KID, MP>(sh, a, (int64_t)blockIdx.x);
 }
 
-template <int KID>
-static void launch_vb(int Mp, int64_t P, hipStream_t st, const VbArgs& a) {
-  const dim3 grid((unsigned)P);
-  if (Mp == 16) vfe_batch_kernel<KID, 16><<<grid, 256, 0, st>>>(a);
-  else if (Mp == 32) vfe_batch_kernel<KID, 32><<<grid, 256, 0, st>>>(a);
-  else vfe_batch_kernel<KID, 64><<<grid, 256, 0, st>>>(a);
-}
-
-template <int KID>
-static int occupancy_vb(int Mp) {
-  int n = 0;
-  hipError_t e;
-  if (Mp == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, vfe_batch_kernel<KID, 16>, 256, 0);
-  else if (Mp == 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, vfe_batch_kernel<KID, 32>, 256, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, vfe_batch_kernel<KID, 64>, 256, 0);
-  return e == hipSuccess ? n : SGP_ERR_LAUNCH;
-}
-
 }  // namespace sgp
 
 using namespace sgp;
@@ -51,12 +33,8 @@ extern "C" size_t sgp_vfe_batch_workspace_bytes(int64_t P, int64_t N, int M, int
 extern "C" int sgp_vfe_batch_occupancy(int M, int kernel_id) {
   const int chk = vb_check(1, 1, M, 1, kernel_id);
   if (chk != SGP_OK) return chk;
-  const int Mp = vb_size_class(M);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: return occupancy_vb<SGP_KERNEL_RBF>(Mp);
-    case SGP_KERNEL_MATERN32: return occupancy_vb<SGP_KERNEL_MATERN32>(Mp);
-    default: return occupancy_vb<SGP_KERNEL_MATERN52>(Mp);
-  }
+  return with_kid_class<16, 32, 64>(kernel_id, vb_size_class(M),
+                                    [](auto kid, auto mp) { return wg_occupancy(vfe_batch_kernel<kid(), mp()>); });
 }
 
 extern "C" int sgp_vfe_eval_batch(const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride, const int* ix,
@@ -76,25 +54,17 @@ extern "C" int sgp_vfe_eval_batch(const double* X, int64_t x_stride, int64_t ldx
   a.N = (int)N, a.M = M, a.d = d, a.want_grad = want_grad ? 1 : 0;
   a.jitter = jitter;
   a.out = out, a.gz = g_Z, a.info = info;
-  hipStream_t st = (hipStream_t)stream;
-  const int Mp = vb_size_class(M);
-  switch (kernel_id) {
-    case SGP_KERNEL_RBF: launch_vb<SGP_KERNEL_RBF>(Mp, P, st, a); break;
-    case SGP_KERNEL_MATERN32: launch_vb<SGP_KERNEL_MATERN32>(Mp, P, st, a); break;
-    default: launch_vb<SGP_KERNEL_MATERN52>(Mp, P, st, a); break;
-  }
+  with_kid_class<16, 32, 64>(kernel_id, vb_size_class(M), [&](auto kid, auto mp) {
+    vfe_batch_kernel<kid(), mp()><<<dim3((unsigned)P), 256, 0, (hipStream_t)stream>>>(a);
+  });
   return check_launch();
 }
 
-// The context twin: the kernel reads no context option, so what a context means here is the device it belongs to.
 extern "C" int sgp_ctx_vfe_eval_batch(sgp_ctx* ctx, const double* X, int64_t x_stride, int64_t ldx, const double* Y, int64_t y_stride,
                                       const int* ix, const int* iy, const double* Z, int64_t z_stride, int64_t ldz, const int* iz,
                                       const double* theta, int64_t P, int64_t N, int M, int d, int kernel_id, double jitter, int want_grad,
                                       double* out, double* g_Z, int* info, void* ws, size_t ws_bytes, sgp_stream_t stream) {
-  if (ctx) {  // (NULL: the default context follows the caller)
-    int dev = -1;
-    if (hipGetDevice(&dev) == hipSuccess && dev != sgp_ctx_device(ctx)) return SGP_ERR_ARG;
-  }
+  if (!ctx_device_matches(ctx)) return SGP_ERR_ARG;
   return sgp_vfe_eval_batch(X, x_stride, ldx, Y, y_stride, ix, iy, Z, z_stride, ldz, iz, theta, P, N, M, d, kernel_id, jitter, want_grad,
                             out, g_Z, info, ws, ws_bytes, stream);
 }

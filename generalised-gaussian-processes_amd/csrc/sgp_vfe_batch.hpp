@@ -12,7 +12,7 @@
 // then L^-T.  No unwhitened M x M matrix is ever applied to K_uf (that order costs cond(K_uu), see the reference's docstring).
 //
 // LDS.  Mp = the size class of M (16, 32 or 64; identity in the padding), every M x M image Mp x (Mp + 2) doubles -- the bank-safe
-// row stride of sgp_exact_batch.hpp.  P holds K -> L -> L^-1 for the whole call, Q holds B -> L_B -> L_B^-1 -> W1.  The two further
+// row stride of sgp_wg_dense.hpp.  P holds K -> L -> L^-1 for the whole call, Q holds B -> L_B -> L_B^-1 -> W1.  The two further
 // images of the middle (B^-1 / C L^-1 and B / C / Kbar_uu) share their bytes with the two row tiles of the passes, which are never
 // alive at the same time.  A row tile is TN = 2048 / Mp rows (128, 64, 32), stored TRANSPOSED, tile[n][m] with the images' stride: in
 // every product  dst^T = Mimg src^T  the contraction index then runs along a row of both operands ("16 rows x 4 consecutive columns").
@@ -30,6 +30,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "../../include/sgp.h"
+#include "sgp_wg_dense.hpp"
 
 #if defined(__HIPCC__)
 #define SGP_VB_HD __host__ __device__
@@ -45,7 +46,7 @@ constexpr int VB_MAXD = 8;
 constexpr int64_t VB_MAXP = (1 << 24) - 1;  // one workgroup per problem: P x 256 work-items stay below the 2^32 of one launch
 constexpr int VB_XLD = VB_MAXD + 1;     // odd stride of the coordinate rows in LDS
 constexpr int VB_TILE_ENTRIES = 2048;   // Mp x TN: 8 entries per thread
-constexpr size_t VB_WS_UNIT = 256;
+constexpr size_t VB_WS_UNIT = WG_WS_UNIT;  // the family's unit (sgp_wg_dense.hpp) under this header's name
 
 // The size class of M (0: none): the launch picks the kernel instantiation by it
 SGP_VB_HD constexpr int vb_size_class(int M) { return M < 1 || M > VB_MAXM ? 0 : (M <= 16 ? 16 : (M <= 32 ? 32 : 64)); }
@@ -408,7 +409,7 @@ __device__ __forceinline__ void vb_eval(VbShared<MP>& sh, const VbArgs& a, int64
 #pragma unroll
   for (int q = 0; q < NACC; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
   double pu = 0.0, pa2 = 0.0, pyy = 0.0;
-  const int kperm = 8 * (l4 & 1) + 4 * (l4 >> 1);  // both operands of A A^T run down a column: sgp_exact_batch.hpp's row permutation
+  const int kperm = 8 * (l4 & 1) + 4 * (l4 >> 1);  // both operands of A A^T run down a column: sgp_wg_dense.hpp's row permutation
   for (int it = 0; it < n_tiles; ++it) {
     const int t0 = it * TN;
     vb_load_rows<MP>(sh, Xp, a.ldx, Yp, t0, N, d);

@@ -55,7 +55,8 @@ def test_new_symbols_are_declared_exported_and_bound(lib):
     assert hasattr(ggp_amd.HipEngine, "exact_nuts_batch") and L.EXACT_NUTS_BAD_START == BAD_START == 1
     assert "#define SGP_EXACT_NUTS_BAD_START 1" in txt
     import ggp_amd.build as B
-    assert [c[1] for c in B.COMPANIONS] == [["sgp_exact_nuts.hip"]] and "sgp_exact_nuts.hip" not in B.SOURCES
+    assert ("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h") in B.COMPANIONS
+    assert [c[1] for c in B.COMPANIONS].count(["sgp_exact_nuts.hip"]) == 1 and "sgp_exact_nuts.hip" not in B.SOURCES
 
 
 def test_the_digest_covers_the_companion_library(tmp_path, monkeypatch):
@@ -64,7 +65,7 @@ def test_the_digest_covers_the_companion_library(tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("_sgp_build_en", os.path.join(ROOT, "generalised-gaussian-processes_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    name, sources, header = b.COMPANIONS[0]
+    (name, sources, header), = [c for c in b.COMPANIONS if c[0] == "libsgp_exact_nuts_hip.so"]
     before = b._companion_digest(b._digest(), sources, header)
     assert before == open(os.path.join(b.CSRC, name + ".sha256")).read().strip()
     work = tmp_path / "pkg" / "csrc"
@@ -77,7 +78,8 @@ def test_the_digest_covers_the_companion_library(tmp_path, monkeypatch):
         shutil.copy(os.path.join(ROOT, "include", h), tmp_path / "include" / h)
     monkeypatch.setattr(b, "CSRC", str(work))
     assert b._companion_digest(b._digest(), sources, header) == before
-    for edited in (work / "sgp_exact_nuts.hip", work / "sgp_exact_target.hpp", work / "sgp_nuts.hpp", tmp_path / "include" / header):
+    for edited in (work / "sgp_exact_nuts.hip", work / "sgp_exact_target.hpp", work / "sgp_nuts.hpp", work / "sgp_wg_dense.hpp",
+                   tmp_path / "include" / header):
         with open(edited, "a") as fh:
             fh.write("// a comment\n")
         after = b._companion_digest(b._digest(), sources, header)

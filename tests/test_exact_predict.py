@@ -168,15 +168,16 @@ def test_new_symbols_are_declared_exported_and_bound(lib):
     assert not any(n in L.EXACT_NUTS_PROTOTYPES for n in NAMES)
     assert hasattr(ggp_amd.HipEngine, "exact_predict_batch") and hasattr(ggp_amd.HipEngine, "exact_mixture")
     import ggp_amd.build as B
-    assert B.COMPANIONS == [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h")]
-    assert [c[1] for c in B.MORE_COMPANIONS] == [["sgp_exact_predict.hip"]] and "sgp_exact_predict.hip" not in B.SOURCES
+    assert B.COMPANIONS[0] == ("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h")
+    assert ("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h") in B.COMPANIONS
+    assert [c[1] for c in B.COMPANIONS].count(["sgp_exact_predict.hip"]) == 1 and "sgp_exact_predict.hip" not in B.SOURCES
 
 
 def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("_sgp_build_ep", os.path.join(ROOT, "generalised-gaussian-processes_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    name, sources, header = b.MORE_COMPANIONS[0]
+    (name, sources, header), = [c for c in b.COMPANIONS if c[0] == "libsgp_exact_predict_hip.so"]
     before = b._companion_digest(b._digest(), sources, header)
     assert before == open(os.path.join(b.CSRC, name + ".sha256")).read().strip()
     work = tmp_path / "pkg" / "csrc"
@@ -189,8 +190,8 @@ def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
         shutil.copy(os.path.join(ROOT, "include", h), tmp_path / "include" / h)
     monkeypatch.setattr(b, "CSRC", str(work))
     assert b._companion_digest(b._digest(), sources, header) == before
-    for edited in (work / "sgp_exact_predict.hip", work / "sgp_exact_predict.hpp", work / "sgp_exact_batch.hpp", work / "sgp_common.hpp",
-                   tmp_path / "include" / header):
+    for edited in (work / "sgp_exact_predict.hip", work / "sgp_exact_predict.hpp", work / "sgp_exact_batch.hpp", work / "sgp_wg_dense.hpp",
+                   work / "sgp_common.hpp", tmp_path / "include" / header):
         with open(edited, "a") as fh:
             fh.write("// a comment\n")
         after = b._companion_digest(b._digest(), sources, header)

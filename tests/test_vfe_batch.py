@@ -53,9 +53,9 @@ def test_new_symbols_are_declared_exported_and_bound(lib):
         assert not any(n in table for n in NAMES)
     assert hasattr(ggp_amd.HipEngine, "vfe_eval_batch")
     import ggp_amd.build as B
-    assert B.COMPANIONS == [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h")]
-    assert B.MORE_COMPANIONS == [("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h")]
-    assert B.SPARSE_COMPANIONS == [("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
+    assert B.COMPANIONS == [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h"),
+                            ("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h"),
+                            ("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
     assert "sgp_vfe_batch.hip" not in B.SOURCES
 
 
@@ -63,7 +63,7 @@ def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("_sgp_build_vb", os.path.join(ROOT, "generalised-gaussian-processes_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    name, sources, header = b.SPARSE_COMPANIONS[0]
+    (name, sources, header), = [c for c in b.COMPANIONS if c[0] == "libsgp_vfe_batch_hip.so"]
     before = b._companion_digest(b._digest(), sources, header)
     assert before == open(os.path.join(b.CSRC, name + ".sha256")).read().strip()
     work = tmp_path / "pkg" / "csrc"
@@ -76,7 +76,8 @@ def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
         shutil.copy(os.path.join(ROOT, "include", h), tmp_path / "include" / h)
     monkeypatch.setattr(b, "CSRC", str(work))
     assert b._companion_digest(b._digest(), sources, header) == before
-    for edited in (work / "sgp_vfe_batch.hip", work / "sgp_vfe_batch.hpp", work / "sgp_common.hpp", tmp_path / "include" / header):
+    for edited in (work / "sgp_vfe_batch.hip", work / "sgp_vfe_batch.hpp", work / "sgp_wg_dense.hpp", work / "sgp_common.hpp",
+                   tmp_path / "include" / header):
         with open(edited, "a") as fh:
             fh.write("// a comment\n")
         after = b._companion_digest(b._digest(), sources, header)
