@@ -19,7 +19,11 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
     ``_hmc_rmse``, one entry per cell);
   * ``--sparse M`` (0 by default): the sparse ML-II estimates beside the exact ones -- the collapsed bound with M inducing inputs
     (``ggp_amd.fit_sgpr_batch``, ``learn_Z=True``: Adam for ``--sparse_steps`` steps, all data sets of a cell in lock step with one
-    launch per step), started at M evenly spaced training inputs; recorded as ``<sweep>_sparse_ls``, ``_sf``, ``_sn``, ``_elbo``.
+    launch per step), started at M evenly spaced training inputs; recorded as ``<sweep>_sparse_ls``, ``_sf``, ``_sn``, ``_elbo``;
+  * ``--sparse M`` together with ``--hmc``: also NUTS over theta of the collapsed bound of every data set at its fitted Z
+    (``SgprBatchResult.sample_nuts``: the reference's ``train_fixed_model`` protocol, all chains of a cell in one device-resident batch),
+    the posterior means of (ls, sig_f, sig_n) recorded beside the sparse ML-II estimates as ``<sweep>_sparse_hmc_ls``, ``_sf``, ``_sn``
+    and ``_seconds``.
 
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
@@ -46,12 +50,15 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
     ``holdout`` = K > 0: K more points are drawn per cell and kept out of the fit and the sampling; res["learn"] (the ML-II plug-in,
     ``Ml2Result.predict``) and res["hmc"] (the mixture over the draws, ``ExactNutsResult.predict``) gain nlpd, rmse: len(cells) x n_sets.
     ``sparse`` = dict(M, steps): also res["sparse"] = dict(ls, sf, sn, elbo: len(cells) x n_sets, seconds), the optimum of the collapsed
-    bound with min(M, n) inducing inputs (it draws nothing from ``rng``)."""
+    bound with min(M, n) inducing inputs (it draws nothing from ``rng``); with ``hmc`` as well, res["sparse_hmc"] = dict(ls, sf, sn:
+    len(cells) x n_sets posterior means of NUTS over theta at the fitted Z, diverging, seconds)."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
     if hmc:
         res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
     if sparse:
         res["sparse"] = {"ls": [], "sf": [], "sn": [], "elbo": [], "seconds": []}
+    if sparse and hmc:
+        res["sparse_hmc"] = {"ls": [], "sf": [], "sn": [], "diverging": [], "seconds": []}
     if holdout:
         for m in ("learn", "hmc") if hmc else ("learn",):
             res[m].update(nlpd=[], rmse=[])
@@ -79,6 +86,12 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r = res["sparse"]
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["elbo"].append(fit.elbo), r["seconds"].append(time.time() - t0)
+            if hmc:
+                post = fit.sample_nuts(hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed)
+                with np.errstate(invalid="ignore"):
+                    mean, r = np.nanmean(np.exp(post.samples), axis=(1, 2)), res["sparse_hmc"]
+                r["ls"].append(mean[:, 0]), r["sf"].append(mean[:, 1]), r["sn"].append(mean[:, 2])
+                r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
         if hmc:
             post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
             mean, r = post.posterior_mean(), res["hmc"]
@@ -111,6 +124,10 @@ def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n
                 for k in ("log_ls", "log_sf", "log_sn"):
                     summary["%s_hmc_mean_%s" % (name, k)] = r[k].mean(1).tolist()
                 summary["%s_hmc_diverging" % name], summary["%s_hmc_seconds" % name] = r["diverging"].tolist(), r["seconds"].tolist()
+                continue
+            if mode == "sparse_hmc":  # the sparse posterior means of the cell's data sets, averaged, beside the sparse optimum's
+                summary["%s_sparse_hmc_mean_log_ls" % name] = np.log(np.nanmean(r["ls"], 1)).tolist()
+                summary["%s_sparse_hmc_diverging" % name], summary["%s_sparse_hmc_seconds" % name] = r["diverging"].tolist(), r["seconds"].tolist()
                 continue
             if mode == "sparse":  # beside ML-II's log of the mean fitted lengthscale: the same figure of the sparse optimum
                 summary["%s_sparse_mean_log_ls" % name] = np.log(np.nanmean(r["ls"], 1)).tolist()

@@ -18,6 +18,7 @@ from .ml2 import Ml2Result, fit_ml2, identification_data, lml_surface  # noqa: F
 from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariationalGP, SparseGPR, StochasticVariationalGP,  # noqa: F401
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
 from .sgpr_batch import SgprBatchResult, elbo_surface, fit_sgpr_batch  # noqa: F401
+from .sgpr_nuts import SgprNutsResult, sample_sgpr_nuts_batch  # noqa: F401
 from .sgp_hmc import (CompositeSgpmcModel, SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments,  # noqa: F401
                       predict_sgpmc, train_sgp_hmc, train_sgp_hmc_composite)
 from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget, SgpmcTargetBase  # noqa: F401

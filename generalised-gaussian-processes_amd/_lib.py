@@ -280,11 +280,28 @@ VFE_BATCH_PROTOTYPES = {
 }
 VFE_BATCH_MAX_M, VFE_BATCH_MAX_N, VFE_BATCH_MAX_D, VFE_BATCH_MAX_P = 64, 65536, 8, 2 ** 24 - 1  # the limits of sgp_vfe_eval_batch
 
+# the companion library libsgp_vfe_nuts_hip.so (include/sgp_vfe_nuts.h): C device-resident NUTS chains over the collapsed bound at fixed
+# inducing inputs, one workgroup each (begin, then advance until all have finished)
+_VN_BEGIN = [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+_VN_ADVANCE = [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+               _i32, _vp, _vp, _sz, _vp]
+VFE_NUTS_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_vfe_nuts_hip.so")
+VFE_NUTS_PROTOTYPES = {
+    "sgp_vfe_nuts_batch_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "sgp_vfe_nuts_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_vfe_nuts_batch_begin": (_i32, _VN_BEGIN),
+    "sgp_ctx_vfe_nuts_batch_begin": (_i32, [_vp] + _VN_BEGIN),
+    "sgp_vfe_nuts_batch_advance": (_i32, _VN_ADVANCE),
+    "sgp_ctx_vfe_nuts_batch_advance": (_i32, [_vp] + _VN_ADVANCE),
+}
+VFE_NUTS_BAD_START = 1  # SGP_VFE_NUTS_BAD_START
+
 # key -> (path, prototypes) of a companion library; _COMPANION_LIBS caches what has been loaded
 _COMPANION_TABLE = {
     "exact_nuts": (EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES),
     "exact_predict": (EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES),
     "vfe_batch": (VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES),
+    "vfe_nuts": (VFE_NUTS_LIB_PATH, VFE_NUTS_PROTOTYPES),
 }
 _LIB = None
 _COMPANION_LIBS = {}
@@ -354,6 +371,11 @@ def load_exact_predict_library():
 def load_vfe_batch_library():
     """The batched collapsed bound's library (include/sgp_vfe_batch.h)."""
     return _load_companion("vfe_batch")
+
+
+def load_vfe_nuts_library():
+    """The batched sparse sampler's library (include/sgp_vfe_nuts.h)."""
+    return _load_companion("vfe_nuts")
 
 
 def check(fn_name: str, status: int):

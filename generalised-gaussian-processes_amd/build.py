@@ -22,6 +22,10 @@ VERSION_SCRIPT = "libsgp.map"
 COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h"),
               ("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h"),
               ("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
+# COMPANIONS is pinned as the literal above by tests/test_vfe_batch.py (exactly those three entries), and existing tests do not change:
+# every companion library added since is registered here instead, and later ones go here too.  build_companions builds both lists
+# by the same rule and with the same digest.
+EXTRA_COMPANIONS = [("libsgp_vfe_nuts_hip.so", ["sgp_vfe_nuts.hip"], "sgp_vfe_nuts.h")]
 PUBLIC_HEADER = os.path.join("..", "..", "include", "sgp.h")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # only the SGP_API symbols of include/sgp.h leave the library
 
@@ -63,7 +67,7 @@ def _companion_digest(core_digest: str, sources, header) -> str:
 def build_companions(force: bool = False, verbose: bool = False):
     """Compile and link every companion library (after the core library, which they link to).  Returns their paths."""
     hipcc, core, paths = None, _digest(), []
-    for name, sources, header in COMPANIONS:
+    for name, sources, header in COMPANIONS + EXTRA_COMPANIONS:
         path = os.path.join(CSRC, name)
         stamp, digest = path + ".sha256", _companion_digest(core, sources, header)
         paths.append(path)

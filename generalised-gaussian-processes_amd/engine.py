@@ -1162,6 +1162,85 @@ class HipEngine:
         return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
                 "draws": counts[1], "info": info.to("cpu"), "launches": launches}
 
+    # Row tiles one resident workgroup walks in a launch of ``vfe_nuts_batch`` by default (an evaluation walks
+    # vb_tiles(N, Mp) row tiles twice and costs at most 24 us per tile in the single-workgroup rows of profiles/vfe_batch_rates.json,
+    # so 4096 tiles keep the longest launch near 0.1 s -- derived from those rows, not fitted to the sampler, whose launches then
+    # measured 60 to 80 ms in profiles/vfe_nuts_rates.json); shared among the waves of workgroups when there are more chains than the
+    # chip holds at a time.
+    VFE_NUTS_LAUNCH_TILES = 4096
+
+    @property
+    def vfe_nuts_lib(self):
+        """The companion library of the batched sparse sampler (include/sgp_vfe_nuts.h), loaded on first use."""
+        return _lib.load_vfe_nuts_library()
+
+    @staticmethod
+    def _vfe_tiles(N: int, M: int) -> int:
+        """vb_tiles(N, Mp) of csrc/sgp_vfe_batch.hpp: the row tiles (2048 / Mp rows each, Mp the size class of M) that cover N rows."""
+        rows = 2048 // (16 if M <= 16 else 32 if M <= 32 else 64)
+        return -(-int(N) // rows)
+
+    def vfe_nuts_evals_per_launch(self, C: int, N: int, M: int, kernel="rbf") -> int:
+        """The default ``evals_per_launch`` of ``vfe_nuts_batch``: ``VFE_NUTS_LAUNCH_TILES`` divided by the number of waves of workgroups
+        C chains make on this device (chains per CU from ``sgp_vfe_nuts_batch_occupancy``), in evaluations of ``vb_tiles(N, Mp)`` row
+        tiles each; never below 1."""
+        per_cu = int(self.vfe_nuts_lib.sgp_vfe_nuts_batch_occupancy(int(M), _kernel_id(kernel)))
+        _lib.check("sgp_vfe_nuts_batch_occupancy", min(per_cu, 0))
+        slots = max(1, per_cu * torch.cuda.get_device_properties(self.device).multi_processor_count)
+        return max(1, self.VFE_NUTS_LAUNCH_TILES // -(-int(C) // slots) // self._vfe_tiles(N, M))
+
+    def vfe_nuts_batch(self, X, Y, Z, q0, seeds, n_tune, n_draws, ix=None, iy=None, iz=None, kernel="rbf", jitter=1e-6, max_treedepth=10,
+                       step_scale=0.25, target_accept=0.8, evals_per_launch=None):
+        """C independent NUTS chains over the collapsed (VFE) bound at fixed inducing inputs, one workgroup each, entirely on the device
+        (include/sgp_vfe_nuts.h: sgp_vfe_nuts_batch_begin / _advance).  X: nX x N x d (or N x d), Y: nY x N (or N), Z: nZ x M x d (or
+        M x d) -- device tensors; chain c samples data set ix[c] with target iy[c] and inducing set iz[c] (None: set 0) from q0[c]
+        (C x (d + 2), unconstrained) with the splitmix64 stream of seeds[c]; ``jitter`` goes on K_uu.  The run is a loop of bounded
+        launches (``evals_per_launch`` evaluations per chain each, default ``vfe_nuts_evals_per_launch``) with one 8-byte read-back per
+        launch; no output but ``seconds`` depends on how it is cut.  Returns host tensors: samples [C, n_draws, d + 2], stats [C,
+        n_draws, 8], seconds [C, n_draws], evaluations [C], draws [C] (int64), info [C] (int32: 0, or ``_lib.VFE_NUTS_BAD_START`` -- no
+        finite density at the start, that chain's rows are NaN), and ``launches``."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        Z = Z if Z.dim() == 3 else Z[None]
+        nX, N, d = X.shape
+        nY, (nZ, M) = Y.shape[0], Z.shape[:2]
+        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z")
+        q0 = torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)).reshape(-1, d + 2)
+        q0 = q0.to(self.device).contiguous()
+        C_ = q0.shape[0]
+        seeds = np.asarray([int(s) & ((1 << 64) - 1) for s in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)], dtype=np.uint64)
+        if Y.shape[1] != N or Z.shape[2] != d or seeds.size != C_ or n_draws < 1 or n_tune < 0:
+            raise ValueError("shapes: X %s, Y %s, Z %s, q0 %s, %d seeds, n_tune %d, n_draws %d"
+                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(q0.shape), seeds.size, n_tune, n_draws))
+        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
+                and 1 <= C_ <= _lib.VFE_BATCH_MAX_P):
+            raise ValueError("vfe_nuts_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d and 1 <= C < 2^24 (got M %d, N %d, d %d, C %d)"
+                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, M, N, d, C_))
+        seeds_d = torch.as_tensor(seeds.view(np.int64)).to(self.device)
+        ix, iy, iz = self._set_index(ix, nX, C_, "ix"), self._set_index(iy, nY, C_, "iy"), self._set_index(iz, nZ, C_, "iz")
+        kid = _kernel_id(kernel)
+        lib = self.vfe_nuts_lib
+        samples, stats, seconds = self.empty(C_, n_draws, d + 2), self.empty(C_, n_draws, 8), self.empty(C_, n_draws)
+        counts = torch.empty(2, C_, dtype=torch.int64, device=self.device)
+        info = torch.empty(C_, dtype=torch.int32, device=self.device)
+        ws = self._workspace("vfe_nuts", lib.sgp_vfe_nuts_batch_workspace_bytes(C_, N, M, d))
+        outs = (self._ptr(samples), self._ptr(stats), self._ptr(seconds), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(info))
+        _lib.check("sgp_vfe_nuts_batch_begin", lib.sgp_ctx_vfe_nuts_batch_begin(
+            self._c(), self._ptr(q0), self._ptr(seeds_d), C_, N, M, d, kid, int(n_tune), int(n_draws), int(max_treedepth),
+            float(step_scale), float(target_accept), *outs, self._ptr(ws), ws.numel(), self._stream()))
+        if evals_per_launch is None:
+            evals_per_launch = self.vfe_nuts_evals_per_launch(C_, N, M, kernel)
+        finished, launches = C.c_int64(0), 0
+        while finished.value < C_:
+            _lib.check("sgp_vfe_nuts_batch_advance", lib.sgp_ctx_vfe_nuts_batch_advance(
+                self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), self._ptr(Z), M * d, d, self._ptr(iz),
+                C_, N, M, d, kid, float(jitter), *outs, int(evals_per_launch), C.byref(finished), self._ptr(ws), ws.numel(),
+                self._stream()))
+            launches += 1
+        counts = counts.to("cpu")
+        return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
+                "draws": counts[1], "info": info.to("cpu"), "launches": launches}
+
     def exact_predict(self, Xs, X, ls, sf2, s2, factors, kernel="rbf", pred_noise=True, full_cov=False):
         """Exact posterior predictive at the rows of Xs from ``exact_eval(..., want_factors=True)``'s factors at the same (X, theta)
         (include/sgp.h: sgp_exact_predict).  Returns (mean, var, cov or None) as device tensors; nothing is synchronised."""

@@ -103,6 +103,22 @@ class SgprBatchResult:
         m.likelihood.noise = float(self.theta[b, d + 1])
         return m
 
+    def sample_nuts(self, n_samples: int, tune: int, chains: int = 1, seed=None, **opts):
+        """NUTS over theta for every data set at its fitted Z -- the reference's ``train_fixed_model`` protocol (ML-II for Z, then NUTS
+        over theta at that Z) for the B data sets at once (``sgpr_nuts.sample_sgpr_nuts_batch``: one device-resident batch of
+        B x chains chains).  The best start's Z, the result's kernel and jitter; every chain starts at the log of the fitted theta,
+        [log ls | log sqrt(sf2) | log sqrt(s2)].  ``opts`` go to ``sample_sgpr_nuts_batch`` (max_treedepth, step_scale, ...).
+        Returns an ``SgprNutsResult``."""
+        from .sgpr_nuts import sample_sgpr_nuts_batch
+        if self.X is None or self.Y is None:
+            raise ValueError("this result does not carry the data")
+        d = self.theta.shape[1] - 2
+        start = np.concatenate([np.log(self.theta[:, :d]), 0.5 * np.log(self.theta[:, d:])], 1)[:, None, :]
+        opts.setdefault("start", np.broadcast_to(start, (self.theta.shape[0], int(chains), d + 2)))
+        opts.setdefault("engine", self.engine)
+        return sample_sgpr_nuts_batch(self.X if self.X.shape[0] > 1 else self.X[0], self.Y, self.Z, n_samples, tune, chains=chains,
+                                      kernel=self.kernel, seed=seed, jitter=self.jitter, **opts)
+
 
 def sgpr_start(X_b, Z_init_b, seed, b, r):
     """Start r of data set b: (raw [d + 2], Z [M x d]).  Start 0 is (0, Z_init); start r >= 1 draws raw ~ N(0, 1) and M distinct rows of
