@@ -23,7 +23,11 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
   * ``--sparse M`` together with ``--hmc``: also NUTS over theta of the collapsed bound of every data set at its fitted Z
     (``SgprBatchResult.sample_nuts``: the reference's ``train_fixed_model`` protocol, all chains of a cell in one device-resident batch),
     the posterior means of (ls, sig_f, sig_n) recorded beside the sparse ML-II estimates as ``<sweep>_sparse_hmc_ls``, ``_sf``, ``_sn``
-    and ``_seconds``.
+    and ``_seconds``;
+  * ``--sparse M`` together with ``--holdout K``: the held-out NLPD and RMSE of the sparse ML-II plug-in (``SgprBatchResult.predict``) and,
+    with ``--hmc``, of the mixture over the sparse NUTS draws (``SgprNutsResult.predict``: one launch of the batched sparse predictive
+    over all draws of a cell), beside the exact ones (summary keys ``<sweep>_sparse_nlpd``, ``_sparse_rmse``, ``_sparse_hmc_nlpd``,
+    ``_sparse_hmc_rmse``, one entry per cell).
 
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
@@ -51,7 +55,8 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
     ``Ml2Result.predict``) and res["hmc"] (the mixture over the draws, ``ExactNutsResult.predict``) gain nlpd, rmse: len(cells) x n_sets.
     ``sparse`` = dict(M, steps): also res["sparse"] = dict(ls, sf, sn, elbo: len(cells) x n_sets, seconds), the optimum of the collapsed
     bound with min(M, n) inducing inputs (it draws nothing from ``rng``); with ``hmc`` as well, res["sparse_hmc"] = dict(ls, sf, sn:
-    len(cells) x n_sets posterior means of NUTS over theta at the fitted Z, diverging, seconds)."""
+    len(cells) x n_sets posterior means of NUTS over theta at the fitted Z, diverging, seconds).  With ``holdout`` both gain nlpd, rmse
+    (``SgprBatchResult.predict``, ``SgprNutsResult.predict``)."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
     if hmc:
         res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
@@ -60,8 +65,9 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
     if sparse and hmc:
         res["sparse_hmc"] = {"ls": [], "sf": [], "sn": [], "diverging": [], "seconds": []}
     if holdout:
-        for m in ("learn", "hmc") if hmc else ("learn",):
-            res[m].update(nlpd=[], rmse=[])
+        for m in ("learn", "hmc", "sparse", "sparse_hmc"):
+            if m in res:
+                res[m].update(nlpd=[], rmse=[])
     data = []
     for _, n, var in cells:
         X, Y, latent = ggp_amd.identification_data(n + holdout, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
@@ -86,12 +92,18 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r = res["sparse"]
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["elbo"].append(fit.elbo), r["seconds"].append(time.time() - t0)
+            if holdout:
+                pred = fit.predict(X_test, Y_test)
+                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
             if hmc:
                 post = fit.sample_nuts(hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed)
                 with np.errstate(invalid="ignore"):
                     mean, r = np.nanmean(np.exp(post.samples), axis=(1, 2)), res["sparse_hmc"]
                 r["ls"].append(mean[:, 0]), r["sf"].append(mean[:, 1]), r["sn"].append(mean[:, 2])
                 r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
+                if holdout:
+                    pred = post.predict(X_test, Y_test)
+                    r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
         if hmc:
             post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
             mean, r = post.posterior_mean(), res["hmc"]
@@ -118,7 +130,7 @@ def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n
             for k, v in r.items():
                 out["%s_%s_%s" % (name, mode, k)] = v
             if "nlpd" in r:  # held-out points: the cell's data sets averaged, the ML-II plug-in (noise learnt) beside the NUTS mixture
-                tag = "hmc" if mode == "hmc" else "ml2"
+                tag = "ml2" if mode == "learn" else mode  # (hmc, sparse, sparse_hmc: under their own names)
                 summary["%s_%s_nlpd" % (name, tag)], summary["%s_%s_rmse" % (name, tag)] = r["nlpd"].mean(1).tolist(), r["rmse"].mean(1).tolist()
             if mode == "hmc":  # the posterior means of the cell's data sets, averaged; beside ML-II's log of the mean fitted lengthscale
                 for k in ("log_ls", "log_sf", "log_sn"):

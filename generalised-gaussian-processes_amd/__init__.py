@@ -19,6 +19,7 @@ from .models import (GPR_HMC, BayesianSparseGPR_HMC, BayesianStochasticVariation
                      VariationalHyperDist, all_in_HMC, full_mixture_posterior_predictive, mixture_posterior_predictive)
 from .sgpr_batch import SgprBatchResult, elbo_surface, fit_sgpr_batch  # noqa: F401
 from .sgpr_nuts import SgprNutsResult, sample_sgpr_nuts_batch  # noqa: F401
+from .sgpr_predict import SgprMixturePredictive, predict_sgpr_batch  # noqa: F401
 from .sgp_hmc import (CompositeSgpmcModel, SgpmcModel, get_posterior_predictive_uncertainty_intervals, likelihood_moments,  # noqa: F401
                       predict_sgpmc, train_sgp_hmc, train_sgp_hmc_composite)
 from .targets import ExactHmcTarget, HmcTarget, JointHmcTarget, SgpmcTarget, SgpmcTargetBase  # noqa: F401

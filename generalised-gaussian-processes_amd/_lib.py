@@ -296,12 +296,26 @@ VFE_NUTS_PROTOTYPES = {
 }
 VFE_NUTS_BAD_START = 1  # SGP_VFE_NUTS_BAD_START
 
+# the companion library libsgp_vfe_predict_hip.so (include/sgp_vfe_predict.h): the predictive of P collapsed sparse GPs in one launch
+# (the mixture over the draws is sgp_exact_mixture_reduce of the exact predictive's library)
+_VP_BATCH = [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _dbl,
+             _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+VFE_PREDICT_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_vfe_predict_hip.so")
+VFE_PREDICT_PROTOTYPES = {
+    "sgp_vfe_predict_batch_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "sgp_vfe_predict_batch_occupancy": (_i32, [_i32, _i32]),
+    "sgp_vfe_predict_batch": (_i32, _VP_BATCH),
+    "sgp_ctx_vfe_predict_batch": (_i32, [_vp] + _VP_BATCH),
+}
+VFE_PREDICT_MAX_T = 32768  # VP_MAXT
+
 # key -> (path, prototypes) of a companion library; _COMPANION_LIBS caches what has been loaded
 _COMPANION_TABLE = {
     "exact_nuts": (EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES),
     "exact_predict": (EXACT_PREDICT_LIB_PATH, EXACT_PREDICT_PROTOTYPES),
     "vfe_batch": (VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES),
     "vfe_nuts": (VFE_NUTS_LIB_PATH, VFE_NUTS_PROTOTYPES),
+    "vfe_predict": (VFE_PREDICT_LIB_PATH, VFE_PREDICT_PROTOTYPES),
 }
 _LIB = None
 _COMPANION_LIBS = {}
@@ -376,6 +390,11 @@ def load_vfe_batch_library():
 def load_vfe_nuts_library():
     """The batched sparse sampler's library (include/sgp_vfe_nuts.h)."""
     return _load_companion("vfe_nuts")
+
+
+def load_vfe_predict_library():
+    """The batched sparse predictive's library (include/sgp_vfe_predict.h)."""
+    return _load_companion("vfe_predict")
 
 
 def check(fn_name: str, status: int):

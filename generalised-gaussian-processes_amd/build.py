@@ -25,7 +25,8 @@ COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nu
 # COMPANIONS is pinned as the literal above by tests/test_vfe_batch.py (exactly those three entries), and existing tests do not change:
 # every companion library added since is registered here instead, and later ones go here too.  build_companions builds both lists
 # by the same rule and with the same digest.
-EXTRA_COMPANIONS = [("libsgp_vfe_nuts_hip.so", ["sgp_vfe_nuts.hip"], "sgp_vfe_nuts.h")]
+EXTRA_COMPANIONS = [("libsgp_vfe_nuts_hip.so", ["sgp_vfe_nuts.hip"], "sgp_vfe_nuts.h"),
+                    ("libsgp_vfe_predict_hip.so", ["sgp_vfe_predict.hip"], "sgp_vfe_predict.h")]
 PUBLIC_HEADER = os.path.join("..", "..", "include", "sgp.h")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # only the SGP_API symbols of include/sgp.h leave the library
 

@@ -1039,6 +1039,50 @@ class HipEngine:
         return out, gz, info
 
     @property
+    def vfe_predict_lib(self):
+        """The companion library of the batched sparse predictive (include/sgp_vfe_predict.h), loaded on first use."""
+        return _lib.load_vfe_predict_library()
+
+    def vfe_predict_batch(self, X, Y, Z, theta, Xs, ix=None, iy=None, iz=None, ixs=None, kernel="rbf", jitter=1e-6, pred_noise=True,
+                          want_bound=True):
+        """The predictive of P collapsed (VFE) sparse GPs in ONE launch, one workgroup per problem (include/sgp_vfe_predict.h:
+        sgp_vfe_predict_batch).  X: nX x N x d (or N x d), Y: nY x N (or N), Z: nZ x M x d (or M x d), Xs: nT x T x d (or T x d), theta:
+        P x (d + 2) rows [ls_1..d | sf2 | s2] -- device tensors; problem p takes data set ix[p], target iy[p], inducing set iz[p] and
+        test set ixs[p] (None: set 0); ``jitter`` goes on K_uu.  Returns device tensors (mean [P, T], var [P, T], bound [P] -- the
+        collapsed bound F of every problem, with the bits ``vfe_eval_batch(want_grad=False)`` gives; None without ``want_bound`` --,
+        info [P] int32); nothing is synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        Z = Z if Z.dim() == 3 else Z[None]
+        Xs = Xs if Xs.dim() == 3 else Xs[None]
+        nX, N, d = X.shape
+        nY, (nZ, M), (nT, T) = Y.shape[0], Z.shape[:2], Xs.shape[:2]
+        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z"), self._chk(theta, "theta"), self._chk(Xs, "Xs")
+        if Y.shape[1] != N or Z.shape[2] != d or Xs.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
+            raise ValueError("shapes: X %s, Y %s, Z %s, Xs %s, theta %s (expected theta P x %d)"
+                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(Xs.shape), tuple(theta.shape), d + 2))
+        P = theta.shape[0]
+        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
+                and 1 <= P <= _lib.VFE_BATCH_MAX_P and 1 <= T <= _lib.VFE_PREDICT_MAX_T):
+            raise ValueError("vfe_predict_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d, 1 <= T <= %d and 1 <= P < 2^24 "
+                             "(got M %d, N %d, d %d, T %d, P %d)"
+                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, _lib.VFE_PREDICT_MAX_T, M, N, d, T, P))
+        ix, iy = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy")
+        iz, ixs = self._set_index(iz, nZ, P, "iz"), self._set_index(ixs, nT, P, "ixs")
+        mean, var = self.empty(P, T), self.empty(P, T)
+        bound = self.empty(P) if want_bound else None
+        info = torch.empty(P, dtype=torch.int32, device=self.device)
+        lib = self.vfe_predict_lib
+        ws = self._workspace("vfe_predict", lib.sgp_vfe_predict_batch_workspace_bytes(P, N, M, d, T))
+        st = lib.sgp_ctx_vfe_predict_batch(
+            self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), self._ptr(Z), M * d, d, self._ptr(iz),
+            self._ptr(Xs), T * d, d, T, self._ptr(ixs), self._ptr(theta), P, N, M, d, _kernel_id(kernel), float(jitter),
+            1 if pred_noise else 0, self._ptr(mean), self._ptr(var), self._ptr(bound), self._ptr(info), self._ptr(ws), ws.numel(),
+            self._stream())
+        _lib.check("sgp_vfe_predict_batch", st)
+        return mean, var, bound, info
+
+    @property
     def exact_predict_lib(self):
         """The companion library of the batched predictive (include/sgp_exact_predict.h), loaded on first use."""
         return _lib.load_exact_predict_library()

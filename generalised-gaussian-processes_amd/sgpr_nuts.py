@@ -70,6 +70,20 @@ class SgprNutsResult:
         with np.errstate(invalid="ignore"):
             return np.nanmean(self.samples, axis=(1, 2))
 
+    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True):
+        """The mixture predictive (``sgpr_predict.predict_sgpr_batch``) over every ``thin``-th draw of every chain of each data set, at
+        the inducing inputs, kernel and jitter the draws were sampled with."""
+        if self.X is None or self.Y is None or self.Z is None or self.kernel is None:
+            raise ValueError("this result does not carry the data it was sampled with (X, Y, Z, kernel, jitter): "
+                             "use predict_sgpr_batch(X, Y, Z, samples, X_test, ...)")
+        if int(thin) < 1:
+            raise ValueError("thin >= 1 (got %r)" % (thin,))
+        from .sgpr_predict import predict_sgpr_batch
+        B, nd = self.samples.shape[0], self.samples.shape[-1]
+        draws = self.samples[:, :, ::int(thin)].reshape(B, -1, nd)
+        return predict_sgpr_batch(self.X, self.Y, self.Z, draws, X_test, Y_test, kernel=self.kernel,
+                                  jitter=1e-6 if self.jitter is None else self.jitter, pred_noise=pred_noise, engine=self.engine)
+
     def model(self, b: int):
         """A ``BayesianSparseGPR_HMC`` over data set b with its inducing inputs Z_b: ``mixture_posterior_predictive(model, X_test,
         traces[b][c])`` runs on it unchanged.  The class is the reference's RBF model, so the result must have been sampled with it."""
