@@ -321,42 +321,13 @@ _LIB = None
 _COMPANION_LIBS = {}
 
 
-def load_library(path: str | None = None):
-    """dlopen the HIP library and bind every prototype; raises SgpLibraryError when anything is missing."""
-    global _LIB
-    if _LIB is not None and path is None:
-        return _LIB
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise SgpLibraryError(
-            "%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(needs hipcc); this package has no CPU fallback." % p)
-    try:
-        lib = C.CDLL(p)
-    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
-        raise SgpLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise SgpLibraryError("%s does not export %s" % (p, name)) from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.sgp_abi_version() != SGP_ABI_VERSION:
-        raise SgpLibraryError("ABI version mismatch: library %d, binding %d" % (lib.sgp_abi_version(), SGP_ABI_VERSION))
-    if path is None:
-        _LIB = lib
-    return lib
+_BUILD_HINT = "Build it with `python -c 'import __graft_entry__ as g; g.build()'`"
 
 
-def _load_companion(key):
-    """dlopen a companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
-    if key in _COMPANION_LIBS:
-        return _COMPANION_LIBS[key]
-    p, prototypes = _COMPANION_TABLE[key]
-    load_library()
+def _bind(p: str, prototypes, missing: str):
+    """dlopen ``p`` and bind every prototype; raises SgpLibraryError when anything is missing.  There is no fallback."""
     if not os.path.exists(p):
-        raise SgpLibraryError("%s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % p)
+        raise SgpLibraryError("%s not found. %s%s" % (p, _BUILD_HINT, missing))
     try:
         lib = C.CDLL(p)
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
@@ -368,8 +339,28 @@ def _load_companion(key):
             raise SgpLibraryError("%s does not export %s" % (p, name)) from e
         fn.restype = res
         fn.argtypes = args
-    _COMPANION_LIBS[key] = lib
     return lib
+
+
+def load_library(path: str | None = None):
+    """dlopen the HIP library and bind every prototype; raises SgpLibraryError when anything is missing."""
+    global _LIB
+    if _LIB is not None and path is None:
+        return _LIB
+    lib = _bind(path or LIB_PATH, PROTOTYPES, " (needs hipcc); this package has no CPU fallback.")
+    if lib.sgp_abi_version() != SGP_ABI_VERSION:
+        raise SgpLibraryError("ABI version mismatch: library %d, binding %d" % (lib.sgp_abi_version(), SGP_ABI_VERSION))
+    if path is None:
+        _LIB = lib
+    return lib
+
+
+def _load_companion(key):
+    """dlopen a companion library (after the core library, which it links to) and bind its prototypes; no fallback either."""
+    if key not in _COMPANION_LIBS:
+        load_library()
+        _COMPANION_LIBS[key] = _bind(*_COMPANION_TABLE[key], ".")
+    return _COMPANION_LIBS[key]
 
 
 def load_exact_nuts_library():

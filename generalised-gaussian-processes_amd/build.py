@@ -17,16 +17,14 @@ LIB_NAME = "libsgp_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ["sgp_ctx.hip", "sgp_suffstats_fwd.hip", "sgp_suffstats_i8.hip", "sgp_suffstats_bwd.hip", "sgp_suffstats_bwd_lo.hip", "sgp_dense.hip", "sgp_tail.hip", "sgp_sgpmc.hip", "sgp_sgpmc_lik.hip", "sgp_sgpmc_mc.hip", "sgp_sgpmc_comp.hip", "sgp_svgp.hip", "sgp_svgp_mc.hip", "sgp_composite.hip", "sgp_small.hip", "sgp_exact.hip", "sgp_exact_batch.hip"]
 VERSION_SCRIPT = "libsgp.map"
-# Companion libraries: (library, sources, public header).  Each is one more shared object beside libsgp_hip.so with a C header of its
-# own, linked to the core library; the core's surface (include/sgp.h) does not grow with them.
+# Companion libraries: (library, sources, public header), in build order.  Each is one more shared object beside libsgp_hip.so with a
+# C header of its own, linked to the core library; the core's surface (include/sgp.h) does not grow with them.  A new one is a row here
+# and a row of _lib._COMPANION_TABLE.
 COMPANIONS = [("libsgp_exact_nuts_hip.so", ["sgp_exact_nuts.hip"], "sgp_exact_nuts.h"),
               ("libsgp_exact_predict_hip.so", ["sgp_exact_predict.hip"], "sgp_exact_predict.h"),
-              ("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h")]
-# COMPANIONS is pinned as the literal above by tests/test_vfe_batch.py (exactly those three entries), and existing tests do not change:
-# every companion library added since is registered here instead, and later ones go here too.  build_companions builds both lists
-# by the same rule and with the same digest.
-EXTRA_COMPANIONS = [("libsgp_vfe_nuts_hip.so", ["sgp_vfe_nuts.hip"], "sgp_vfe_nuts.h"),
-                    ("libsgp_vfe_predict_hip.so", ["sgp_vfe_predict.hip"], "sgp_vfe_predict.h")]
+              ("libsgp_vfe_batch_hip.so", ["sgp_vfe_batch.hip"], "sgp_vfe_batch.h"),
+              ("libsgp_vfe_nuts_hip.so", ["sgp_vfe_nuts.hip"], "sgp_vfe_nuts.h"),
+              ("libsgp_vfe_predict_hip.so", ["sgp_vfe_predict.hip"], "sgp_vfe_predict.h")]
 PUBLIC_HEADER = os.path.join("..", "..", "include", "sgp.h")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]  # only the SGP_API symbols of include/sgp.h leave the library
 
@@ -65,75 +63,54 @@ def _companion_digest(core_digest: str, sources, header) -> str:
     return h.hexdigest()
 
 
-def build_companions(force: bool = False, verbose: bool = False):
-    """Compile and link every companion library (after the core library, which they link to).  Returns their paths."""
-    hipcc, core, paths = None, _digest(), []
-    for name, sources, header in COMPANIONS + EXTRA_COMPANIONS:
-        path = os.path.join(CSRC, name)
-        stamp, digest = path + ".sha256", _companion_digest(core, sources, header)
-        paths.append(path)
-        if not force and os.path.exists(path) and os.path.exists(stamp):
-            with open(stamp) as fh:
-                if fh.read().strip() == digest:
-                    continue
-        hipcc = hipcc or _hipcc()
-        objs = []
-        for src in sources:
-            obj = os.path.join(CSRC, src.replace(".hip", ".o"))
-            cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
-            cmd += os.environ.get("SGP_EXTRA_HIPCC_FLAGS", "").split()
-            if verbose:
-                print(" ".join(cmd), file=sys.stderr)
-            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            if r.returncode != 0:
-                raise RuntimeError("hipcc failed on %s:\n%s" % (src, r.stdout))
-            objs.append(obj)
-        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, VERSION_SCRIPT),
-               "-Wl,-rpath,$ORIGIN", "-o", path] + objs + ["-L" + CSRC, "-l:" + LIB_NAME]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link of %s failed:\n%s" % (name, r.stdout))
-        with open(stamp, "w") as fh:
-            fh.write(digest)
-    return paths
-
-
-def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile every HIP translation unit for gfx950 and link them into csrc/libsgp_hip.so, then the companion libraries."""
-    _build_core(force, verbose)
-    build_companions(force, verbose)
-    return LIB_PATH
-
-
-def _build_core(force: bool = False, verbose: bool = False) -> str:
-    stamp = LIB_PATH + ".sha256"
-    digest = _digest()
-    if not force and os.path.exists(LIB_PATH) and os.path.exists(stamp):
+def _compile_and_link(path, sources, digest, force, verbose, parallel=False, to_core=False):
+    """Brings the shared object ``path`` up to date with ``digest`` (kept beside it in ``path``.sha256): every source to an object
+    file (all at once with ``parallel``), then one link -- ``to_core``: against libsgp_hip.so beside it."""
+    stamp = path + ".sha256"
+    if not force and os.path.exists(path) and os.path.exists(stamp):
         with open(stamp) as fh:
             if fh.read().strip() == digest:
-                return LIB_PATH
+                return path
     hipcc = _hipcc()
-    objs = []
-    procs = []
-    for src in SOURCES:
+    objs, running = [], []
+
+    def finish(src, proc):
+        out, _ = proc.communicate()
+        if proc.returncode != 0:
+            raise RuntimeError("hipcc failed on %s:\n%s" % (src, out))
+    for src in sources:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
         cmd += os.environ.get("SGP_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds (tools/ab_build.sh); empty for the product
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+        running.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         objs.append(obj)
-    for src, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError("hipcc failed on %s:\n%s" % (src, out))
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, VERSION_SCRIPT),
-           "-o", LIB_PATH] + objs
+        if not parallel:
+            finish(*running.pop())
+    for job in running:
+        finish(*job)
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, VERSION_SCRIPT)]
+    cmd += (["-Wl,-rpath,$ORIGIN"] if to_core else []) + ["-o", path] + objs + (["-L" + CSRC, "-l:" + LIB_NAME] if to_core else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError("link failed:\n" + r.stdout)
+        raise RuntimeError(("link of %s failed:\n" % os.path.basename(path) if to_core else "link failed:\n") + r.stdout)
     with open(stamp, "w") as fh:
         fh.write(digest)
+    return path
+
+
+def build_companions(force: bool = False, verbose: bool = False):
+    """Compile and link every companion library (after the core library, which they link to).  Returns their paths."""
+    core = _digest()
+    return [_compile_and_link(os.path.join(CSRC, name), sources, _companion_digest(core, sources, header), force, verbose, to_core=True)
+            for name, sources, header in COMPANIONS]
+
+
+def build_library(force: bool = False, verbose: bool = False) -> str:
+    """Compile every HIP translation unit for gfx950 and link them into csrc/libsgp_hip.so, then the companion libraries."""
+    _compile_and_link(LIB_PATH, SOURCES, _digest(), force, verbose, parallel=True)
+    build_companions(force, verbose)
     return LIB_PATH
 
 

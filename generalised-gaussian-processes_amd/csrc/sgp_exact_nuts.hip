@@ -260,8 +260,8 @@ extern "C" int sgp_exact_nuts_batch_begin(const double* q0, const uint64_t* seed
                                           size_t ws_bytes, sgp_stream_t stream) {
   const int chk = exact_nuts_check(C, N, d, kernel_id);
   if (chk != SGP_OK && chk != SGP_ERR_DIM) return chk;
-  if (!q0 || !seed || !samples || !stats || !seconds || !evaluations || !draws || !info || n_tune < 0 || n_draws < 0 ||
-      max_treedepth < 0 || max_treedepth > EN_MAX_TREEDEPTH || !(step_scale > 0.0) || !(target_accept > 0.0 && target_accept < 1.0))
+  if (!q0 || !seed || !samples || !stats || !seconds || !evaluations || !draws || !info ||
+      !nuts_params_ok(n_tune, n_draws, max_treedepth, EN_MAX_TREEDEPTH, step_scale, target_accept))
     return SGP_ERR_ARG;
   if (chk != SGP_OK) return chk;
   if (!ws || ws_bytes < sgp_exact_nuts_batch_workspace_bytes(C, N, d)) return SGP_ERR_WORKSPACE;
@@ -289,12 +289,7 @@ extern "C" int sgp_exact_nuts_batch_advance(const double* X, int64_t x_stride, i
   with_kid_class<32, 64, 128>(kernel_id, eb_size_class(N), [&](auto kid, auto np) {
     exact_nuts_kernel<kid(), np()><<<dim3((unsigned)C), 256, 0, st>>>(a);
   });
-  if (check_launch() != SGP_OK) return SGP_ERR_LAUNCH;
-  unsigned long long done = 0;  // the one read-back of a launch: how many chains have finished
-  if (hipMemcpyAsync(&done, a.finished, sizeof(done), hipMemcpyDeviceToHost, st) != hipSuccess) return SGP_ERR_LAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return SGP_ERR_LAUNCH;
-  *finished = (int64_t)done;
-  return SGP_OK;
+  return nuts_read_finished(a.finished, finished, st);
 }
 
 extern "C" int sgp_ctx_exact_nuts_batch_begin(sgp_ctx* ctx, const double* q0, const uint64_t* seed, int64_t C, int N, int d, int kernel_id,

@@ -258,8 +258,8 @@ extern "C" int sgp_vfe_nuts_batch_begin(const double* q0, const uint64_t* seed, 
                                         void* ws, size_t ws_bytes, sgp_stream_t stream) {
   const int chk = vb_check(C, N, M, d, kernel_id);
   if (chk != SGP_OK && chk != SGP_ERR_DIM) return chk;
-  if (!q0 || !seed || !samples || !stats || !seconds || !evaluations || !draws || !info || n_tune < 0 || n_draws < 0 ||
-      max_treedepth < 0 || max_treedepth > VN_MAX_TREEDEPTH || !(step_scale > 0.0) || !(target_accept > 0.0 && target_accept < 1.0))
+  if (!q0 || !seed || !samples || !stats || !seconds || !evaluations || !draws || !info ||
+      !nuts_params_ok(n_tune, n_draws, max_treedepth, VN_MAX_TREEDEPTH, step_scale, target_accept))
     return SGP_ERR_ARG;
   if (chk != SGP_OK) return chk;
   if (!ws || ws_bytes < sgp_vfe_nuts_batch_workspace_bytes(C, N, M, d)) return SGP_ERR_WORKSPACE;
@@ -293,12 +293,7 @@ extern "C" int sgp_vfe_nuts_batch_advance(const double* X, int64_t x_stride, int
   with_kid_class<16, 32, 64>(kernel_id, vb_size_class(M), [&](auto kid, auto mp) {
     vfe_nuts_kernel<kid(), mp()><<<dim3((unsigned)C), 256, 0, st>>>(a);
   });
-  if (check_launch() != SGP_OK) return SGP_ERR_LAUNCH;
-  unsigned long long done = 0;  // the one read-back of a launch: how many chains have finished
-  if (hipMemcpyAsync(&done, a.finished, sizeof(done), hipMemcpyDeviceToHost, st) != hipSuccess) return SGP_ERR_LAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return SGP_ERR_LAUNCH;
-  *finished = (int64_t)done;
-  return SGP_OK;
+  return nuts_read_finished(a.finished, finished, st);
 }
 
 extern "C" int sgp_ctx_vfe_nuts_batch_begin(sgp_ctx* ctx, const double* q0, const uint64_t* seed, int64_t C, int64_t N, int M, int d,

@@ -70,5 +70,23 @@ inline bool ctx_device_matches(const sgp_ctx* ctx) {
   return !ctx || hipGetDevice(&dev) != hipSuccess || dev == sgp_ctx_device(ctx);
 }
 
+// ---- the host half the two device-resident samplers (sgp_exact_nuts.hip, sgp_vfe_nuts.hip) share ----
+
+// The sampler parameters a *_nuts_batch_begin accepts (a NaN fails every comparison); `depth_limit` is the library's own
+inline bool nuts_params_ok(int n_tune, int n_draws, int max_treedepth, int depth_limit, double step_scale, double target_accept) {
+  return n_tune >= 0 && n_draws >= 0 && max_treedepth >= 0 && max_treedepth <= depth_limit && step_scale > 0.0 && target_accept > 0.0 &&
+         target_accept < 1.0;
+}
+
+// The tail of a *_nuts_batch_advance: the launch's status, then the one read-back of a launch -- how many chains have finished
+inline int nuts_read_finished(const unsigned long long* counter, int64_t* finished, hipStream_t st) {
+  if (check_launch() != SGP_OK) return SGP_ERR_LAUNCH;
+  unsigned long long done = 0;
+  if (hipMemcpyAsync(&done, counter, sizeof(done), hipMemcpyDeviceToHost, st) != hipSuccess) return SGP_ERR_LAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return SGP_ERR_LAUNCH;
+  *finished = (int64_t)done;
+  return SGP_OK;
+}
+
 }  // namespace sgp
 #endif  // __HIPCC__

@@ -41,6 +41,15 @@ def _likelihood_id(likelihood) -> int:
     return _lib.LIKELIHOOD_IDS[name]
 
 
+_F64 = torch.float64
+
+
+def _chk(device, t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype is not _F64 or t.device != device or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float64 tensor on %s (got %s, %s)" % (name, device, t.dtype, t.device))
+    return t
+
+
 class HipEngine:
     """Calls the HIP library on ``device`` (default: current CUDA device).  No CPU fallback.
 
@@ -139,9 +148,7 @@ class HipEngine:
         return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.device)).cuda_stream)
 
     def _chk(self, t: torch.Tensor, name: str) -> torch.Tensor:
-        if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous float64 tensor on %s (got %s, %s)" % (name, self.device, t.dtype, t.device))
-        return t
+        return _chk(self.device, t, name)
 
     @staticmethod
     def hyper_len(kernel, d: int) -> int:
@@ -961,34 +968,90 @@ class HipEngine:
             res["factors"] = factors
         return res
 
-    def _set_index(self, idx, n_sets: int, P: int, name: str):
-        """ix / iy of ``exact_eval_batch`` as a device int32 tensor of P entries, or None.  A host sequence is range-checked here (it
+    # ------------------------------------------------------------------ the one-workgroup-per-problem libraries: their shared frame
+    def _companion_lib(key, what):  # noqa: N805 - builds the properties below
+        return property(lambda self: _lib._load_companion(key), doc="The companion library of %s, loaded on first use." % what)
+
+    exact_nuts_lib = _companion_lib("exact_nuts", "the batched sampler (include/sgp_exact_nuts.h)")
+    exact_predict_lib = _companion_lib("exact_predict", "the batched predictive (include/sgp_exact_predict.h)")
+    vfe_batch_lib = _companion_lib("vfe_batch", "the batched collapsed bound (include/sgp_vfe_batch.h)")
+    vfe_nuts_lib = _companion_lib("vfe_nuts", "the batched sparse sampler (include/sgp_vfe_nuts.h)")
+    vfe_predict_lib = _companion_lib("vfe_predict", "the batched sparse predictive (include/sgp_vfe_predict.h)")
+    del _companion_lib
+
+    @staticmethod
+    def _set_index(device, idx, name: str, n_sets: int, P: int):
+        """A set index (ix / iy / iz / ixs) as a device int32 tensor of P entries, or None.  A host sequence is range-checked here (it
         costs nothing); a device tensor is taken as it is -- the caller answers for its range, nothing is copied to the host."""
         if idx is None:
             return None
-        if isinstance(idx, torch.Tensor) and idx.device == self.device:
+        if isinstance(idx, torch.Tensor) and idx.device == device:
             if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != P:
                 raise ValueError("%s must be a contiguous int32 tensor of %d entries" % (name, P))
             return idx
         host = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx).reshape(-1)
         if host.size != P or (P and (host.min() < 0 or host.max() >= n_sets)):
             raise ValueError("%s must hold %d indices in [0, %d)" % (name, P, n_sets))
-        return torch.as_tensor(host.astype(np.int32), device=self.device)
+        return torch.as_tensor(host.astype(np.int32), device=device)
+
+    @staticmethod
+    def _batch_intake(device, X, Y, Z=None, theta=None, Xs=None, idx=(), limits=None, own=None):
+        """The intake of every batched entry point, by the names of its tensors: X (sets x N x d), Y (sets x N) and, where the caller
+        has them, Z (sets x M x d), Xs (sets x T x d) -- a tensor one rank short is lifted to one set -- and theta (P x (d + 2), taken
+        as it is).  Every tensor must be contiguous float64 on ``device``.  A sampler has no theta and passes ``own`` = (its P, whether
+        its own arguments fit, the tail of the refusal) instead.  What does not fit is refused with "shapes: X ..., Y ..., ..." over
+        exactly the tensors passed (theta last).  Then the VFE family's ``limits`` = (entry point, "P" or "C") where given
+        (``_vfe_limits``), and the set indices ``idx`` -- ix, iy[, iz][, ixs]: one per tensor passed but theta -- through
+        ``_set_index``.  Returns ((X, Y, Z, Xs) as lifted, the indices, (N, d, M, T, P)); None for what was not passed.  It runs on
+        CPU tensors as well."""
+        X = X if X.dim() == 3 else X[None]
+        Y = Y if Y.dim() == 2 else Y[None]
+        nX, N, d = X.shape
+        _chk(device, X, "X"), _chk(device, Y, "Y")
+        shape = Y.shape
+        sets, ok, M, T = [("ix", nX), ("iy", shape[0])], shape[1] == N, None, None
+        if Z is not None:
+            Z = _chk(device, Z if Z.dim() == 3 else Z[None], "Z")
+            shape = Z.shape
+            sets.append(("iz", shape[0]))
+            M, ok = shape[1], ok and shape[2] == d
+        if theta is not None:
+            _chk(device, theta, "theta")
+        if Xs is not None:
+            Xs = _chk(device, Xs if Xs.dim() == 3 else Xs[None], "Xs")
+            shape = Xs.shape
+            sets.append(("ixs", shape[0]))
+            T, ok = shape[1], ok and shape[2] == d
+        if theta is None:
+            P, fits, tail = own
+            ok = ok and fits
+        elif ok and theta.dim() == 2 and theta.shape[1] == d + 2:
+            P = theta.shape[0]
+        else:
+            ok, tail = False, ", theta %s (expected theta P x %d)" % (tuple(theta.shape), d + 2)
+        if not ok:
+            passed = [(n, t) for n, t in (("X", X), ("Y", Y), ("Z", Z), ("Xs", Xs)) if t is not None]
+            raise ValueError("shapes: " + ", ".join("%s %s" % (n, tuple(t.shape)) for n, t in passed) + tail)
+        if limits is not None:
+            HipEngine._vfe_limits(limits[0], limits[1], M, N, d, P, T)
+        return (X, Y, Z, Xs), [HipEngine._set_index(device, i, *s, P) for i, s in zip(idx, sets)], (N, d, M, T, P)
+
+    @staticmethod
+    def _vfe_limits(fn: str, count: str, M, N, d, P, T=None):
+        """The limits of the collapsed-bound family (``_lib.VFE_BATCH_MAX_*``, and VFE_PREDICT_MAX_T where there is a T), refused in
+        the words of the entry point ``fn`` that counts its problems as ``count`` ("P" or "C")."""
+        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
+                and 1 <= P <= _lib.VFE_BATCH_MAX_P and (T is None or 1 <= T <= _lib.VFE_PREDICT_MAX_T)):
+            lim, got = (", 1 <= T <= %d and" % _lib.VFE_PREDICT_MAX_T, ", T %d" % T) if T is not None else (" and", "")
+            raise ValueError("%s takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d%s 1 <= %s < 2^24 (got M %d, N %d, d %d%s, %s %d)"
+                             % (fn, _lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, lim, count, M, N, d, got, count, P))
 
     def exact_eval_batch(self, X, Y, theta, ix=None, iy=None, kernel="rbf", want_grad=True):
         """P exact marginal likelihoods in ONE launch (include/sgp.h: sgp_exact_eval_batch).  X: nX x N x d (or N x d), Y: nY x N (or
         N), theta: P x (d + 2) rows [ls_1..d | sf2 | s2] -- device tensors; problem p takes data set ix[p] and target iy[p] (None: set
         0).  Returns device tensors (F [P], out [P, 4], grads [P, d + 2] or None, info [P] int32); nothing is synchronised and nothing
         is copied to the host.  A problem with info != 0 has NaN rows."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        nX, N, d = X.shape
-        nY = Y.shape[0]
-        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(theta, "theta")
-        if Y.shape[1] != N or theta.dim() != 2 or theta.shape[1] != d + 2:
-            raise ValueError("shapes: X %s, Y %s, theta %s (expected theta P x %d)" % (tuple(X.shape), tuple(Y.shape), tuple(theta.shape), d + 2))
-        P = theta.shape[0]
-        ix, iy = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy")
+        (X, Y, _, _), (ix, iy), (N, d, _, _, P) = self._batch_intake(self.device, X, Y, theta=theta, idx=(ix, iy))
         out = self.empty(P, 4)
         grads = self.empty(P, d + 2) if want_grad else None
         info = torch.empty(P, dtype=torch.int32, device=self.device)
@@ -1000,32 +1063,13 @@ class HipEngine:
         _lib.check("sgp_exact_eval_batch", st)
         return out[:, 0], out, grads, info
 
-    @property
-    def vfe_batch_lib(self):
-        """The companion library of the batched collapsed bound (include/sgp_vfe_batch.h), loaded on first use."""
-        return _lib.load_vfe_batch_library()
-
     def vfe_eval_batch(self, X, Y, Z, theta, ix=None, iy=None, iz=None, kernel="rbf", jitter=1e-6, want_grad=True, want_gz=False):
         """P collapsed (VFE) bounds with their gradients in ONE launch, one workgroup per problem (include/sgp_vfe_batch.h:
         sgp_vfe_eval_batch).  X: nX x N x d (or N x d), Y: nY x N (or N), Z: nZ x M x d (or M x d), theta: P x (d + 2) rows [ls_1..d |
         sf2 | s2] -- device tensors; problem p takes data set ix[p], target iy[p] and inducing set iz[p] (None: set 0).  Returns device
         tensors (out [P, d + 5] = [F | dF/dls | dF/dsf2 | dF/ds2 | logmarg | trace], g_Z [P, M, d] or None, info [P] int32); nothing is
         synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        Z = Z if Z.dim() == 3 else Z[None]
-        nX, N, d = X.shape
-        nY, (nZ, M) = Y.shape[0], Z.shape[:2]
-        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z"), self._chk(theta, "theta")
-        if Y.shape[1] != N or Z.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
-            raise ValueError("shapes: X %s, Y %s, Z %s, theta %s (expected theta P x %d)"
-                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(theta.shape), d + 2))
-        P = theta.shape[0]
-        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
-                and 1 <= P <= _lib.VFE_BATCH_MAX_P):
-            raise ValueError("vfe_eval_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d and 1 <= P < 2^24 (got M %d, N %d, d %d, P %d)"
-                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, M, N, d, P))
-        ix, iy, iz = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy"), self._set_index(iz, nZ, P, "iz")
+        (X, Y, Z, _), (ix, iy, iz), (N, d, M, _, P) = self._batch_intake(self.device, X, Y, Z, theta, None, (ix, iy, iz), ("vfe_eval_batch", "P"))
         out = self.empty(P, d + 5)
         gz = self.empty(P, M, d) if want_grad and want_gz else None
         info = torch.empty(P, dtype=torch.int32, device=self.device)
@@ -1038,11 +1082,6 @@ class HipEngine:
         _lib.check("sgp_vfe_eval_batch", st)
         return out, gz, info
 
-    @property
-    def vfe_predict_lib(self):
-        """The companion library of the batched sparse predictive (include/sgp_vfe_predict.h), loaded on first use."""
-        return _lib.load_vfe_predict_library()
-
     def vfe_predict_batch(self, X, Y, Z, theta, Xs, ix=None, iy=None, iz=None, ixs=None, kernel="rbf", jitter=1e-6, pred_noise=True,
                           want_bound=True):
         """The predictive of P collapsed (VFE) sparse GPs in ONE launch, one workgroup per problem (include/sgp_vfe_predict.h:
@@ -1051,24 +1090,8 @@ class HipEngine:
         test set ixs[p] (None: set 0); ``jitter`` goes on K_uu.  Returns device tensors (mean [P, T], var [P, T], bound [P] -- the
         collapsed bound F of every problem, with the bits ``vfe_eval_batch(want_grad=False)`` gives; None without ``want_bound`` --,
         info [P] int32); nothing is synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        Z = Z if Z.dim() == 3 else Z[None]
-        Xs = Xs if Xs.dim() == 3 else Xs[None]
-        nX, N, d = X.shape
-        nY, (nZ, M), (nT, T) = Y.shape[0], Z.shape[:2], Xs.shape[:2]
-        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z"), self._chk(theta, "theta"), self._chk(Xs, "Xs")
-        if Y.shape[1] != N or Z.shape[2] != d or Xs.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
-            raise ValueError("shapes: X %s, Y %s, Z %s, Xs %s, theta %s (expected theta P x %d)"
-                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(Xs.shape), tuple(theta.shape), d + 2))
-        P = theta.shape[0]
-        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
-                and 1 <= P <= _lib.VFE_BATCH_MAX_P and 1 <= T <= _lib.VFE_PREDICT_MAX_T):
-            raise ValueError("vfe_predict_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d, 1 <= T <= %d and 1 <= P < 2^24 "
-                             "(got M %d, N %d, d %d, T %d, P %d)"
-                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, _lib.VFE_PREDICT_MAX_T, M, N, d, T, P))
-        ix, iy = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy")
-        iz, ixs = self._set_index(iz, nZ, P, "iz"), self._set_index(ixs, nT, P, "ixs")
+        (X, Y, Z, Xs), (ix, iy, iz, ixs), (N, d, M, T, P) = self._batch_intake(
+            self.device, X, Y, Z, theta, Xs, (ix, iy, iz, ixs), ("vfe_predict_batch", "P"))
         mean, var = self.empty(P, T), self.empty(P, T)
         bound = self.empty(P) if want_bound else None
         info = torch.empty(P, dtype=torch.int32, device=self.device)
@@ -1082,27 +1105,12 @@ class HipEngine:
         _lib.check("sgp_vfe_predict_batch", st)
         return mean, var, bound, info
 
-    @property
-    def exact_predict_lib(self):
-        """The companion library of the batched predictive (include/sgp_exact_predict.h), loaded on first use."""
-        return _lib.load_exact_predict_library()
-
     def exact_predict_batch(self, X, Y, theta, Xs, ix=None, iy=None, ixs=None, kernel="rbf", pred_noise=True):
         """The exact-GP predictive of P problems in ONE launch (include/sgp_exact_predict.h: sgp_exact_predict_batch).  X: nX x N x d (or
         N x d), Y: nY x N (or N), Xs: nT x T x d (or T x d), theta: P x (d + 2) rows [ls_1..d | sf2 | s2] -- device tensors; problem p
         takes data set ix[p], target iy[p] and test set ixs[p] (None: set 0).  Returns device tensors (mean [P, T], var [P, T], info
         [P] int32); nothing is synchronised and nothing is copied to the host.  A problem with info != 0 has NaN rows."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        Xs = Xs if Xs.dim() == 3 else Xs[None]
-        nX, N, d = X.shape
-        nY, (nT, T) = Y.shape[0], Xs.shape[:2]
-        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(theta, "theta"), self._chk(Xs, "Xs")
-        if Y.shape[1] != N or Xs.shape[2] != d or theta.dim() != 2 or theta.shape[1] != d + 2:
-            raise ValueError("shapes: X %s, Y %s, Xs %s, theta %s (expected theta P x %d)"
-                             % (tuple(X.shape), tuple(Y.shape), tuple(Xs.shape), tuple(theta.shape), d + 2))
-        P = theta.shape[0]
-        ix, iy, ixs = self._set_index(ix, nX, P, "ix"), self._set_index(iy, nY, P, "iy"), self._set_index(ixs, nT, P, "ixs")
+        (X, Y, _, Xs), (ix, iy, ixs), (N, d, _, T, P) = self._batch_intake(self.device, X, Y, theta=theta, Xs=Xs, idx=(ix, iy, ixs))
         mean, var = self.empty(P, T), self.empty(P, T)
         info = torch.empty(P, dtype=torch.int32, device=self.device)
         lib = self.exact_predict_lib
@@ -1144,23 +1152,63 @@ class HipEngine:
         _lib.check("sgp_exact_mixture_reduce", st)
         return {"mean": mm, "var": mv, "logpdf": lp, "mean_logpdf": mlp, "kept": kept}
 
+    def _launch_budget(self, budget: int, lib, occupancy: str, size: int, C: int, kernel) -> int:
+        """``budget`` divided by the number of waves of workgroups C chains make on this device (chains per CU from the library's
+        ``occupancy`` query at ``size``)."""
+        per_cu = int(getattr(lib, occupancy)(int(size), _kernel_id(kernel)))
+        _lib.check(occupancy, min(per_cu, 0))
+        slots = max(1, per_cu * torch.cuda.get_device_properties(self.device).multi_processor_count)
+        return budget // -(-int(C) // slots)
+
+    def _nuts_batch(self, ws_key, ws_bytes, begin, advance, budget, X, Y, Z, idx, limits, q0, seeds, n_tune, n_draws, kernel, jitter,
+                    max_treedepth, step_scale, target_accept, evals_per_launch):
+        """The driver of the device-resident samplers: the intake of the data, q0 and the seeds, the output buffers, begin, the loop of
+        bounded launches with its one 8-byte read-back each, and the host dict.  The caller supplies its library's workspace query
+        (cached as ``ws_key``), its ``begin`` and ``advance`` as (name for the status check, bound function) and its default
+        ``budget(C, N, M)`` of evaluations per launch; with a Z the C calls carry M and the inducing sets."""
+        d = X.shape[-1]
+        q0 = torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)).reshape(-1, d + 2)
+        q0 = q0.to(self.device).contiguous()
+        C_ = q0.shape[0]
+        seeds = np.asarray([int(s) & ((1 << 64) - 1) for s in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)], dtype=np.uint64)
+        own = (C_, seeds.size == C_ and n_draws >= 1 and n_tune >= 0,
+               ", q0 %s, %d seeds, n_tune %d, n_draws %d" % (tuple(q0.shape), seeds.size, n_tune, n_draws))
+        (X, Y, Z, _), idx, (N, d, M, _, _) = self._batch_intake(self.device, X, Y, Z, idx=idx, limits=limits, own=own)
+        seeds_d = torch.as_tensor(seeds.view(np.int64)).to(self.device)
+        kid = _kernel_id(kernel)
+        dims = (C_, N, d) if Z is None else (C_, N, M, d)
+        samples, stats, seconds = self.empty(C_, n_draws, d + 2), self.empty(C_, n_draws, 8), self.empty(C_, n_draws)
+        counts = torch.empty(2, C_, dtype=torch.int64, device=self.device)
+        info = torch.empty(C_, dtype=torch.int32, device=self.device)
+        ws = self._workspace(ws_key, ws_bytes(*dims))
+        outs = (self._ptr(samples), self._ptr(stats), self._ptr(seconds), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(info))
+        _lib.check(begin[0], begin[1](
+            self._c(), self._ptr(q0), self._ptr(seeds_d), *dims, kid, int(n_tune), int(n_draws), int(max_treedepth), float(step_scale),
+            float(target_accept), *outs, self._ptr(ws), ws.numel(), self._stream()))
+        if evals_per_launch is None:
+            evals_per_launch = budget(C_, N, M)
+        data = [self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(idx[0]), self._ptr(idx[1])]
+        if Z is not None:
+            data += [self._ptr(Z), M * d, d, self._ptr(idx[2])]
+        finished, launches = C.c_int64(0), 0
+        while finished.value < C_:
+            _lib.check(advance[0], advance[1](
+                self._c(), *data, *dims, kid, float(jitter), *outs, int(evals_per_launch), C.byref(finished), self._ptr(ws), ws.numel(),
+                self._stream()))
+            launches += 1
+        counts = counts.to("cpu")
+        return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
+                "draws": counts[1], "info": info.to("cpu"), "launches": launches}
+
     # Evaluations one resident workgroup runs back to back in a launch of ``exact_nuts_batch`` by default (DESIGN 6e-3: 1024 x the
     # measured 138 us per evaluation of one chain at N = 128 keeps the longest launch near 0.14 s); shared among the waves of workgroups
     # when there are more chains than the chip holds at a time.
     EXACT_NUTS_LAUNCH_EVALS = 1024
 
-    @property
-    def exact_nuts_lib(self):
-        """The companion library of the batched sampler (include/sgp_exact_nuts.h), loaded on first use."""
-        return _lib.load_exact_nuts_library()
-
     def exact_nuts_evals_per_launch(self, C: int, N: int, kernel="rbf") -> int:
         """The default ``evals_per_launch`` of ``exact_nuts_batch``: ``EXACT_NUTS_LAUNCH_EVALS`` divided by the number of waves of
         workgroups C chains make on this device (chains per CU from ``sgp_exact_nuts_batch_occupancy``)."""
-        per_cu = int(self.exact_nuts_lib.sgp_exact_nuts_batch_occupancy(int(N), _kernel_id(kernel)))
-        _lib.check("sgp_exact_nuts_batch_occupancy", min(per_cu, 0))
-        slots = max(1, per_cu * torch.cuda.get_device_properties(self.device).multi_processor_count)
-        return max(1, self.EXACT_NUTS_LAUNCH_EVALS // -(-int(C) // slots))
+        return max(1, self._launch_budget(self.EXACT_NUTS_LAUNCH_EVALS, self.exact_nuts_lib, "sgp_exact_nuts_batch_occupancy", N, C, kernel))
 
     def exact_nuts_batch(self, X, Y, q0, seeds, n_tune, n_draws, ix=None, iy=None, kernel="rbf", jitter=0.0, max_treedepth=10,
                          step_scale=0.25, target_accept=0.8, evals_per_launch=None):
@@ -1171,40 +1219,11 @@ class HipEngine:
         8-byte read-back per launch; no output but ``seconds`` depends on how it is cut.  Returns host tensors: samples [C, n_draws,
         d + 2], stats [C, n_draws, 8], seconds [C, n_draws], evaluations [C], draws [C] (int64), info [C] (int32: 0, or
         ``_lib.EXACT_NUTS_BAD_START`` -- no finite density at the start, that chain's rows are NaN), and ``launches``."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        nX, N, d = X.shape
-        nY = Y.shape[0]
-        self._chk(X, "X"), self._chk(Y, "Y")
-        q0 = torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)).reshape(-1, d + 2)
-        q0 = q0.to(self.device).contiguous()
-        C_ = q0.shape[0]
-        seeds = np.asarray([int(s) & ((1 << 64) - 1) for s in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)], dtype=np.uint64)
-        if Y.shape[1] != N or seeds.size != C_ or n_draws < 1 or n_tune < 0:
-            raise ValueError("shapes: X %s, Y %s, q0 %s, %d seeds, n_tune %d, n_draws %d" % (tuple(X.shape), tuple(Y.shape), tuple(q0.shape),
-                                                                                            seeds.size, n_tune, n_draws))
-        seeds_d = torch.as_tensor(seeds.view(np.int64)).to(self.device)
-        ix, iy = self._set_index(ix, nX, C_, "ix"), self._set_index(iy, nY, C_, "iy")
-        kid = _kernel_id(kernel)
-        samples, stats, seconds = self.empty(C_, n_draws, d + 2), self.empty(C_, n_draws, 8), self.empty(C_, n_draws)
-        counts = torch.empty(2, C_, dtype=torch.int64, device=self.device)
-        info = torch.empty(C_, dtype=torch.int32, device=self.device)
-        ws = self._workspace("exact_nuts", self.exact_nuts_lib.sgp_exact_nuts_batch_workspace_bytes(C_, N, d))
-        outs = (self._ptr(samples), self._ptr(stats), self._ptr(seconds), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(info))
-        _lib.check("sgp_exact_nuts_batch_begin", self.exact_nuts_lib.sgp_ctx_exact_nuts_batch_begin(
-            self._c(), self._ptr(q0), self._ptr(seeds_d), C_, N, d, kid, int(n_tune), int(n_draws), int(max_treedepth), float(step_scale),
-            float(target_accept), *outs, self._ptr(ws), ws.numel(), self._stream()))
-        if evals_per_launch is None:
-            evals_per_launch = self.exact_nuts_evals_per_launch(C_, N, kernel)
-        finished, launches = C.c_int64(0), 0
-        while finished.value < C_:
-            _lib.check("sgp_exact_nuts_batch_advance", self.exact_nuts_lib.sgp_ctx_exact_nuts_batch_advance(
-                self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), C_, N, d, kid, float(jitter), *outs,
-                int(evals_per_launch), C.byref(finished), self._ptr(ws), ws.numel(), self._stream()))
-            launches += 1
-        counts = counts.to("cpu")
-        return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
-                "draws": counts[1], "info": info.to("cpu"), "launches": launches}
+        lib = self.exact_nuts_lib
+        return self._nuts_batch(
+            "exact_nuts", lib.sgp_exact_nuts_batch_workspace_bytes, ("sgp_exact_nuts_batch_begin", lib.sgp_ctx_exact_nuts_batch_begin),
+            ("sgp_exact_nuts_batch_advance", lib.sgp_ctx_exact_nuts_batch_advance), lambda C_, N, M: self.exact_nuts_evals_per_launch(C_, N, kernel),
+            X, Y, None, (ix, iy), None, q0, seeds, n_tune, n_draws, kernel, jitter, max_treedepth, step_scale, target_accept, evals_per_launch)
 
     # Row tiles one resident workgroup walks in a launch of ``vfe_nuts_batch`` by default (DESIGN 6e-7: an evaluation walks
     # vb_tiles(N, Mp) row tiles twice and costs at most 24 us per tile in the single-workgroup rows of profiles/vfe_batch_rates.json,
@@ -1212,11 +1231,6 @@ class HipEngine:
     # measured 60 to 80 ms in profiles/vfe_nuts_rates.json); shared among the waves of workgroups when there are more chains than the
     # chip holds at a time.
     VFE_NUTS_LAUNCH_TILES = 4096
-
-    @property
-    def vfe_nuts_lib(self):
-        """The companion library of the batched sparse sampler (include/sgp_vfe_nuts.h), loaded on first use."""
-        return _lib.load_vfe_nuts_library()
 
     @staticmethod
     def _vfe_tiles(N: int, M: int) -> int:
@@ -1228,10 +1242,8 @@ class HipEngine:
         """The default ``evals_per_launch`` of ``vfe_nuts_batch``: ``VFE_NUTS_LAUNCH_TILES`` divided by the number of waves of workgroups
         C chains make on this device (chains per CU from ``sgp_vfe_nuts_batch_occupancy``), in evaluations of ``vb_tiles(N, Mp)`` row
         tiles each; never below 1."""
-        per_cu = int(self.vfe_nuts_lib.sgp_vfe_nuts_batch_occupancy(int(M), _kernel_id(kernel)))
-        _lib.check("sgp_vfe_nuts_batch_occupancy", min(per_cu, 0))
-        slots = max(1, per_cu * torch.cuda.get_device_properties(self.device).multi_processor_count)
-        return max(1, self.VFE_NUTS_LAUNCH_TILES // -(-int(C) // slots) // self._vfe_tiles(N, M))
+        tiles = self._launch_budget(self.VFE_NUTS_LAUNCH_TILES, self.vfe_nuts_lib, "sgp_vfe_nuts_batch_occupancy", M, C, kernel)
+        return max(1, tiles // self._vfe_tiles(N, M))
 
     def vfe_nuts_batch(self, X, Y, Z, q0, seeds, n_tune, n_draws, ix=None, iy=None, iz=None, kernel="rbf", jitter=1e-6, max_treedepth=10,
                        step_scale=0.25, target_accept=0.8, evals_per_launch=None):
@@ -1243,47 +1255,12 @@ class HipEngine:
         launch; no output but ``seconds`` depends on how it is cut.  Returns host tensors: samples [C, n_draws, d + 2], stats [C,
         n_draws, 8], seconds [C, n_draws], evaluations [C], draws [C] (int64), info [C] (int32: 0, or ``_lib.VFE_NUTS_BAD_START`` -- no
         finite density at the start, that chain's rows are NaN), and ``launches``."""
-        X = X if X.dim() == 3 else X[None]
-        Y = Y if Y.dim() == 2 else Y[None]
-        Z = Z if Z.dim() == 3 else Z[None]
-        nX, N, d = X.shape
-        nY, (nZ, M) = Y.shape[0], Z.shape[:2]
-        self._chk(X, "X"), self._chk(Y, "Y"), self._chk(Z, "Z")
-        q0 = torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)).reshape(-1, d + 2)
-        q0 = q0.to(self.device).contiguous()
-        C_ = q0.shape[0]
-        seeds = np.asarray([int(s) & ((1 << 64) - 1) for s in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)], dtype=np.uint64)
-        if Y.shape[1] != N or Z.shape[2] != d or seeds.size != C_ or n_draws < 1 or n_tune < 0:
-            raise ValueError("shapes: X %s, Y %s, Z %s, q0 %s, %d seeds, n_tune %d, n_draws %d"
-                             % (tuple(X.shape), tuple(Y.shape), tuple(Z.shape), tuple(q0.shape), seeds.size, n_tune, n_draws))
-        if not (1 <= M <= _lib.VFE_BATCH_MAX_M and 1 <= N <= _lib.VFE_BATCH_MAX_N and 1 <= d <= _lib.VFE_BATCH_MAX_D
-                and 1 <= C_ <= _lib.VFE_BATCH_MAX_P):
-            raise ValueError("vfe_nuts_batch takes 1 <= M <= %d, 1 <= N <= %d, 1 <= d <= %d and 1 <= C < 2^24 (got M %d, N %d, d %d, C %d)"
-                             % (_lib.VFE_BATCH_MAX_M, _lib.VFE_BATCH_MAX_N, _lib.VFE_BATCH_MAX_D, M, N, d, C_))
-        seeds_d = torch.as_tensor(seeds.view(np.int64)).to(self.device)
-        ix, iy, iz = self._set_index(ix, nX, C_, "ix"), self._set_index(iy, nY, C_, "iy"), self._set_index(iz, nZ, C_, "iz")
-        kid = _kernel_id(kernel)
         lib = self.vfe_nuts_lib
-        samples, stats, seconds = self.empty(C_, n_draws, d + 2), self.empty(C_, n_draws, 8), self.empty(C_, n_draws)
-        counts = torch.empty(2, C_, dtype=torch.int64, device=self.device)
-        info = torch.empty(C_, dtype=torch.int32, device=self.device)
-        ws = self._workspace("vfe_nuts", lib.sgp_vfe_nuts_batch_workspace_bytes(C_, N, M, d))
-        outs = (self._ptr(samples), self._ptr(stats), self._ptr(seconds), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(info))
-        _lib.check("sgp_vfe_nuts_batch_begin", lib.sgp_ctx_vfe_nuts_batch_begin(
-            self._c(), self._ptr(q0), self._ptr(seeds_d), C_, N, M, d, kid, int(n_tune), int(n_draws), int(max_treedepth),
-            float(step_scale), float(target_accept), *outs, self._ptr(ws), ws.numel(), self._stream()))
-        if evals_per_launch is None:
-            evals_per_launch = self.vfe_nuts_evals_per_launch(C_, N, M, kernel)
-        finished, launches = C.c_int64(0), 0
-        while finished.value < C_:
-            _lib.check("sgp_vfe_nuts_batch_advance", lib.sgp_ctx_vfe_nuts_batch_advance(
-                self._c(), self._ptr(X), N * d, d, self._ptr(Y), N, self._ptr(ix), self._ptr(iy), self._ptr(Z), M * d, d, self._ptr(iz),
-                C_, N, M, d, kid, float(jitter), *outs, int(evals_per_launch), C.byref(finished), self._ptr(ws), ws.numel(),
-                self._stream()))
-            launches += 1
-        counts = counts.to("cpu")
-        return {"samples": samples.to("cpu"), "stats": stats.to("cpu"), "seconds": seconds.to("cpu"), "evaluations": counts[0],
-                "draws": counts[1], "info": info.to("cpu"), "launches": launches}
+        return self._nuts_batch(
+            "vfe_nuts", lib.sgp_vfe_nuts_batch_workspace_bytes, ("sgp_vfe_nuts_batch_begin", lib.sgp_ctx_vfe_nuts_batch_begin),
+            ("sgp_vfe_nuts_batch_advance", lib.sgp_ctx_vfe_nuts_batch_advance), lambda C_, N, M: self.vfe_nuts_evals_per_launch(C_, N, M, kernel),
+            X, Y, Z, (ix, iy, iz), ("vfe_nuts_batch", "C"), q0, seeds, n_tune, n_draws, kernel, jitter, max_treedepth, step_scale,
+            target_accept, evals_per_launch)
 
     def exact_predict(self, Xs, X, ls, sf2, s2, factors, kernel="rbf", pred_noise=True, full_cov=False):
         """Exact posterior predictive at the rows of Xs from ``exact_eval(..., want_factors=True)``'s factors at the same (X, theta)

@@ -13,6 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .exact_nuts import _host, _host_sets
 from .ml2 import MAX_D, MAX_N, _check_kernel, _dev, _engine
 
 NOISE_FLOOR_VAR, NOISE_FLOOR_SD = 1e-4, 0.01  # the reference's rule: a draw with sig_n^2 < 1e-4 is predicted at sig_n = 0.01
@@ -42,27 +43,17 @@ class ExactMixturePredictive:
         return np.sqrt(((self.mean - Y_test) ** 2).mean(1)) * Y_std
 
 
-def _host(a):
-    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
-
-
-def predict_theta_batch(X, Y, theta, X_test, Y_test=None, kernel="rbf", pred_noise=True, engine=None) -> ExactMixturePredictive:
-    """The mixture predictive at constrained rows: ``theta`` is B x S x (d + 2), rows [ls_1..d | sf2 | s2], used as they are."""
+def _mixture_frame(result, run, X, Y, Z, limits, theta, X_test, Y_test, kernel, engine):
+    """What the mixture predictives share: the host intake, the set index of every draw, the engine's batched predictive --
+    ``run(eng, data, theta, Xt, idx)`` with ``data`` = (X, Y[, Z]) on the device and ``idx`` = (ix, iy[, iz], ixs), giving (mean, var,
+    bound or None, info) --, ``exact_mixture`` over the draws of each data set, and the ONE host copy into ``result``."""
     _check_kernel(kernel)
     eng = _engine(engine)
-    Yh = _host(Y)
-    Yh = Yh[None] if Yh.ndim == 1 else Yh
-    Xh, Xt = _host(X), _host(X_test)
-    Xh = Xh[:, None] if Xh.ndim == 1 else Xh
+    Xh, Yh, Zh, B, N, d = _host_sets(X, Y, Z, limits)
+    Xt = _host(X_test)
     Xt = Xt[:, None] if Xt.ndim == 1 else Xt
     theta = np.asarray(theta, dtype=np.float64)
-    B, N = Yh.shape
-    d = Xh.shape[-1]
-    shared_x, shared_t = Xh.ndim == 2, Xt.ndim == 2
-    if not 1 <= N <= MAX_N or not 1 <= d <= MAX_D or Xh.shape[-2] != N or (not shared_x and Xh.shape[0] != B):
-        raise ValueError("X must be N x d or B x N x d with 1 <= N <= %d, 1 <= d <= %d, Y B x N (got X %s, Y %s)"
-                         % (MAX_N, MAX_D, Xh.shape, Yh.shape))
-    if Xt.shape[-1] != d or (not shared_t and Xt.shape[0] != B):
+    if Xt.shape[-1] != d or (Xt.ndim != 2 and Xt.shape[0] != B):
         raise ValueError("X_test must be T x %d or %d x T x %d (got %s)" % (d, B, d, Xt.shape))
     if theta.ndim != 3 or theta.shape[0] != B or theta.shape[2] != d + 2 or theta.shape[1] < 1:
         raise ValueError("the draws must be %d x S x %d (got %s)" % (B, d + 2, theta.shape))
@@ -73,22 +64,30 @@ def predict_theta_batch(X, Y, theta, X_test, Y_test=None, kernel="rbf", pred_noi
         if Yt.shape != (B, T):
             raise ValueError("Y_test must be %d x %d (got %s)" % (B, T, Yt.shape))
     set_of = np.repeat(np.arange(B, dtype=np.int32), S)
-    mean, var, info = eng.exact_predict_batch(_dev(Xh, eng), _dev(Yh, eng), _dev(theta.reshape(B * S, d + 2), eng), _dev(Xt, eng),
-                                              ix=None if shared_x else set_of, iy=set_of, ixs=None if shared_t else set_of,
-                                              kernel=kernel, pred_noise=pred_noise)
+    held = [h for h in (Xh, Yh, Zh) if h is not None]
+    idx = tuple(set_of if h is Yh or h.ndim != 2 else None for h in held + [Xt])  # a shared X, Z or X_test is set 0 for every draw
+    mean, var, bound, info = run(eng, tuple(_dev(h, eng) for h in held), _dev(theta.reshape(B * S, d + 2), eng), _dev(Xt, eng), idx)
     mix = eng.exact_mixture(mean, var, info, [b * S for b in range(B + 1)], Ytest=None if Y_test is None else _dev(Yt, eng))
     # one host copy: everything in one float64 buffer (the integer columns are exact in it)
-    parts = [mean.reshape(-1), var.reshape(-1), info.reshape(-1).to(torch.float64), mix["mean"].reshape(-1), mix["var"].reshape(-1),
-             mix["kept"].reshape(-1).to(torch.float64)]
+    parts = {"draw_mean": (mean, (B, S, T)), "draw_var": (var, (B, S, T)), "info": (info, (B, S))}
+    if bound is not None:
+        parts["bound"] = (bound, (B, S))
+    parts.update(mean=(mix["mean"], (B, T)), var=(mix["var"], (B, T)), kept=(mix["kept"], (B,)))
     if Y_test is not None:
-        parts += [mix["logpdf"].reshape(-1), mix["mean_logpdf"].reshape(-1)]
-    host = torch.cat(parts).cpu().numpy()
-    cuts = np.cumsum([0, B * S * T, B * S * T, B * S, B * T, B * T, B] + ([B * T, B * T] if Y_test is not None else []))
-    seg = [host[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
-    return ExactMixturePredictive(
-        mean=seg[3].reshape(B, T), var=seg[4].reshape(B, T), draw_mean=seg[0].reshape(B, S, T), draw_var=seg[1].reshape(B, S, T),
-        info=seg[2].astype(np.int32).reshape(B, S), kept=seg[5].astype(np.int64),
-        logpdf=seg[6].reshape(B, T) if Y_test is not None else None, mean_logpdf=seg[7].reshape(B, T) if Y_test is not None else None)
+        parts.update(logpdf=(mix["logpdf"], (B, T)), mean_logpdf=(mix["mean_logpdf"], (B, T)))
+    host = torch.cat([t.reshape(-1).to(torch.float64) for t, _ in parts.values()]).cpu().numpy()
+    cuts = np.cumsum([0] + [int(np.prod(shape)) for _, shape in parts.values()])
+    seg = {k: host[cuts[i]:cuts[i + 1]].reshape(shape) for i, (k, (_, shape)) in enumerate(parts.items())}
+    seg.update(info=seg["info"].astype(np.int32), kept=seg["kept"].astype(np.int64))
+    return result(**{"logpdf": None, "mean_logpdf": None, **seg})
+
+
+def predict_theta_batch(X, Y, theta, X_test, Y_test=None, kernel="rbf", pred_noise=True, engine=None) -> ExactMixturePredictive:
+    """The mixture predictive at constrained rows: ``theta`` is B x S x (d + 2), rows [ls_1..d | sf2 | s2], used as they are."""
+    def run(eng, data, th, Xt, idx):
+        mean, var, info = eng.exact_predict_batch(*data, th, Xt, ix=idx[0], iy=idx[1], ixs=idx[2], kernel=kernel, pred_noise=pred_noise)
+        return mean, var, None, info
+    return _mixture_frame(ExactMixturePredictive, run, X, Y, None, (MAX_N, MAX_D, None), theta, X_test, Y_test, kernel, engine)
 
 
 def constrain_samples(samples, jitter=0.0):

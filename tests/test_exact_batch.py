@@ -270,3 +270,70 @@ def test_host_side_limits_of_the_batch_need_no_device():
     for P, N, d, kid, status in ((2 ** 24, 10, 2, 0, -2), (2, 129, 2, 0, -2), (2, 10, 9, 0, -2), (2, 10, 2, 3, -1), (0, 10, 2, 0, -1)):
         assert lib.sgp_exact_eval_batch(null, 0, d, null, 0, null, null, null, P, N, d, kid, 1, null, null, null, null, 0, null) == status
     assert lib.sgp_exact_batch_occupancy(129, 0) == -2 and lib.sgp_exact_batch_occupancy(10, 3) == -1
+
+
+# ---------------------------------------------------------------------------------------------------------------- the shared intake
+def test_the_batched_intake_lifts_checks_and_names_what_it_was_given():
+    """``HipEngine._batch_intake`` and ``_set_index`` -- the intake of all six batched entry points -- on CPU tensors."""
+    import torch
+    cpu, f64 = torch.device("cpu"), torch.float64
+    intake, set_index = ggp_amd.HipEngine._batch_intake, ggp_amd.HipEngine._set_index
+    N, d, M, T, P = 6, 2, 3, 4, 5
+    X, Y, Z, Xs, theta = (torch.zeros(s, dtype=f64) for s in ((N, d), (N,), (M, d), (T, d), (P, d + 2)))
+    # one rank short is one set; a set-major tensor is taken as it is; None passes through
+    tensors, idx, dims = intake(cpu, X, Y, Z, theta, Xs, (None, [0] * P, None, None))
+    assert [tuple(t.shape) for t in tensors] == [(1, N, d), (1, N), (1, M, d), (1, T, d)]
+    assert all(a.data_ptr() == b.data_ptr() for a, b in zip(tensors, (X, Y, Z, Xs)))
+    assert idx[0] is idx[2] is idx[3] is None and idx[1].dtype == torch.int32 and idx[1].tolist() == [0] * P and dims == (N, d, M, T, P)
+    X3, Y2, Z3, Xs3 = X.expand(2, N, d).contiguous(), Y.expand(3, N).contiguous(), Z.expand(4, M, d).contiguous(), Xs.expand(7, T, d).contiguous()
+    top = ([1] * P, [2] * P, [3] * P, [6] * P)  # the last set of each of the 2, 3, 4 and 7
+    tensors, idx, dims = intake(cpu, X3, Y2, Z3, theta, Xs3, top)
+    assert all(a is b for a, b in zip(tensors, (X3, Y2, Z3, Xs3)))
+    assert [i.tolist() for i in idx] == [list(i) for i in top] and dims == (N, d, M, T, P)
+    for k, name in enumerate(("ix", "iy", "iz", "ixs")):  # each index against the set count of its own tensor
+        with pytest.raises(ValueError, match=r"%s must hold 5 indices in \[0, %d\)" % (name, top[k][0] + 1)):
+            intake(cpu, X3, Y2, Z3, theta, Xs3, top[:k] + ([top[k][0] + 1] * P,) + top[k + 1:])
+    with pytest.raises(ValueError, match=r"ixs must hold 5 indices in \[0, 7\)"):  # without a Z the third index is the test set's
+        intake(cpu, X3, Y2, theta=theta, Xs=Xs3, idx=(None, None, [7] * P))
+    tensors, idx, dims = intake(cpu, X, Y2, theta=theta, idx=(None, None))
+    assert tensors[1] is Y2 and tensors[2:] == (None, None) and idx == [None, None] and dims == (N, d, None, None, P)
+    # the refusal names exactly the tensors passed, theta last
+    for kw, text in (
+            (dict(Y=torch.zeros(N + 1, dtype=f64), theta=theta), "shapes: X (1, 6, 2), Y (1, 7), theta (5, 4) (expected theta P x 4)"),
+            (dict(Y=Y, Z=torch.zeros(M, d + 1, dtype=f64), theta=theta),
+             "shapes: X (1, 6, 2), Y (1, 6), Z (1, 3, 3), theta (5, 4) (expected theta P x 4)"),
+            (dict(Y=Y, theta=theta, Xs=torch.zeros(2, T, d - 1, dtype=f64)),
+             "shapes: X (1, 6, 2), Y (1, 6), Xs (2, 4, 1), theta (5, 4) (expected theta P x 4)"),
+            (dict(Y=Y, Z=Z, theta=torch.zeros(P, d + 1, dtype=f64), Xs=Xs),
+             "shapes: X (1, 6, 2), Y (1, 6), Z (1, 3, 2), Xs (1, 4, 2), theta (5, 3) (expected theta P x 4)"),
+            (dict(Y=Y, theta=torch.zeros(d + 2, dtype=f64)), "shapes: X (1, 6, 2), Y (1, 6), theta (4,) (expected theta P x 4)")):
+        with pytest.raises(ValueError) as e:
+            intake(cpu, X, **kw)
+        assert str(e.value) == text
+    # a sampler has no theta: its own arguments decide with the shapes and end the text; the VFE limits come after the shapes
+    assert intake(cpu, X, Y, Z, own=(9, True, ""))[2] == (N, d, M, None, 9)
+    for kw, fits, text in ((dict(Y=Y), False, "shapes: X (1, 6, 2), Y (1, 6), q0 (2, 4), 3 seeds, n_tune 0, n_draws 1"),
+                           (dict(Y=Y[:-1], Z=Z), True, "shapes: X (1, 6, 2), Y (1, 5), Z (1, 3, 2), q0 (2, 4), 3 seeds, n_tune 0, n_draws 1")):
+        with pytest.raises(ValueError) as e:
+            intake(cpu, X, own=(2, fits, ", q0 (2, 4), 3 seeds, n_tune 0, n_draws 1"), **kw)
+        assert str(e.value) == text
+    with pytest.raises(ValueError, match=r"vfe_nuts_batch takes 1 <= M <= 64, .* and 1 <= C < 2\^24 \(got M 3, N 6, d 2, C 0\)"):
+        intake(cpu, X, Y, Z, limits=("vfe_nuts_batch", "C"), own=(0, True, ""))
+    with pytest.raises(ValueError, match=r"vfe_predict_batch takes .* 1 <= d <= 8, 1 <= T <= 32768 and 1 <= P < 2\^24 \(got M 65, N 6, d 2, T 4, P 5\)"):
+        intake(cpu, X, Y, torch.zeros(65, d, dtype=f64), theta, Xs, limits=("vfe_predict_batch", "P"))
+    for bad in (X.float(), X.t()):
+        with pytest.raises(ValueError, match="X must be a contiguous float64 tensor on cpu"):
+            intake(cpu, bad, Y, theta=theta)
+    # the set indices: None passes through, a host sequence is range-checked, a tensor on the device is taken as it is
+    assert set_index(cpu, None, "ix", 3, P) is None
+    got = set_index(cpu, [0, 2, 1, 2, 0], "iy", 3, P)
+    assert got.dtype == torch.int32 and got.tolist() == [0, 2, 1, 2, 0]
+    own = torch.zeros(P, dtype=torch.int32)
+    assert set_index(cpu, own, "iz", 3, P) is own
+    for idx, text in (([0, 1], "ix must hold 5 indices in [0, 3)"), ([0, 1, 2, 3, 0], "ix must hold 5 indices in [0, 3)"),
+                      (np.array([0, -1, 0, 0, 0]), "ix must hold 5 indices in [0, 3)"),
+                      (torch.zeros(P, dtype=torch.int64), "ix must be a contiguous int32 tensor of 5 entries"),
+                      (torch.zeros(P + 1, dtype=torch.int32), "ix must be a contiguous int32 tensor of 5 entries")):
+        with pytest.raises(ValueError) as e:
+            set_index(cpu, idx, "ix", 3, P)
+        assert str(e.value) == text

@@ -204,8 +204,8 @@ def test_new_symbols_are_declared_exported_and_bound(lib):
     assert L._COMPANION_TABLE["vfe_predict"] == (L.VFE_PREDICT_LIB_PATH, L.VFE_PREDICT_PROTOTYPES) and L.VFE_PREDICT_MAX_T == 32768
     assert hasattr(ggp_amd.HipEngine, "vfe_predict_batch") and hasattr(ggp_amd.HipEngine, "vfe_predict_lib")
     import ggp_amd.build as B
-    assert ENTRY in B.EXTRA_COMPANIONS and ENTRY not in B.COMPANIONS and len(B.COMPANIONS) == 3
-    assert [c[1] for c in B.COMPANIONS + B.EXTRA_COMPANIONS].count(["sgp_vfe_predict.hip"]) == 1 and "sgp_vfe_predict.hip" not in B.SOURCES
+    assert B.COMPANIONS.count(ENTRY) == 1
+    assert [c[1] for c in B.COMPANIONS].count(["sgp_vfe_predict.hip"]) == 1 and "sgp_vfe_predict.hip" not in B.SOURCES
 
 
 def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
@@ -213,7 +213,7 @@ def test_the_digest_covers_the_new_library(lib, tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("_sgp_build_vp", os.path.join(ROOT, "generalised-gaussian-processes_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    (name, sources, header), = [c for c in b.EXTRA_COMPANIONS if c[0] == "libsgp_vfe_predict_hip.so"]
+    (name, sources, header), = [c for c in b.COMPANIONS if c[0] == "libsgp_vfe_predict_hip.so"]
     before = b._companion_digest(b._digest(), sources, header)
     assert before == open(os.path.join(b.CSRC, name + ".sha256")).read().strip()
     work = tmp_path / "pkg" / "csrc"
