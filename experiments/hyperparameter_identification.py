@@ -27,7 +27,12 @@ on the batched exact-GP entry point: where ML-II fails, and why one samples thet
   * ``--sparse M`` together with ``--holdout K``: the held-out NLPD and RMSE of the sparse ML-II plug-in (``SgprBatchResult.predict``) and,
     with ``--hmc``, of the mixture over the sparse NUTS draws (``SgprNutsResult.predict``: one launch of the batched sparse predictive
     over all draws of a cell), beside the exact ones (summary keys ``<sweep>_sparse_nlpd``, ``_sparse_rmse``, ``_sparse_hmc_nlpd``,
-    ``_sparse_hmc_rmse``, one entry per cell).
+    ``_sparse_hmc_rmse``, one entry per cell);
+  * ``--calibration`` together with ``--holdout K``: every held-out predictive also gives the mixture's 2.5 % and 97.5 % quantiles and
+    its CDF at the targets (``probs=(0.025, 0.975)``: one more launch each) -- the share of held-out targets inside the central 95 %
+    interval and that interval's mean width, the plug-in beside the mixture (summary keys ``<sweep>_ml2_cover95``, ``_hmc_cover95``,
+    ``_ml2_width95``, ``_hmc_width95`` and, with ``--sparse M``, ``_sparse_cover95``, ``_sparse_hmc_cover95``, ``_sparse_width95``,
+    ``_sparse_hmc_width95``, one entry per cell).
 
 Writes ``<out>/hyperparameter_identification.npz`` (every fitted theta and surface) and ``.json`` (the averages the reference plots);
 figures are drawn only if matplotlib imports.  ``engine`` (tests: a CPU double) defaults to the HIP engine.
@@ -45,9 +50,10 @@ import ggp_amd  # noqa: E402
 
 TRUE = {"sig_sd": 5.0, "lengthscale": 2.0, "noise_sd": 1.0}
 AMP_BOUNDS = (1e-5, 1e5)
+CALIBRATION_PROBS = (0.025, 0.975)
 
 
-def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None, holdout=0, sparse=None):
+def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, seed, hmc=None, holdout=0, sparse=None, calibration=False):
     """cells: [(label, n_train, noise variance)].  Fits every cell with the noise fixed at its true variance and with the noise learnt.
     Returns {mode: dict(ls, sf, sn: len(cells) x n_sets, n_batches)} and the data.  ``hmc`` = dict(chains, tune, draws): also
     res["hmc"] = dict(log_ls, log_sf, log_sn: len(cells) x n_sets posterior means, diverging: the cell's share of diverging draws).
@@ -56,7 +62,8 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
     ``sparse`` = dict(M, steps): also res["sparse"] = dict(ls, sf, sn, elbo: len(cells) x n_sets, seconds), the optimum of the collapsed
     bound with min(M, n) inducing inputs (it draws nothing from ``rng``); with ``hmc`` as well, res["sparse_hmc"] = dict(ls, sf, sn:
     len(cells) x n_sets posterior means of NUTS over theta at the fitted Z, diverging, seconds).  With ``holdout`` both gain nlpd, rmse
-    (``SgprBatchResult.predict``, ``SgprNutsResult.predict``)."""
+    (``SgprBatchResult.predict``, ``SgprNutsResult.predict``).  ``calibration`` (with ``holdout``): every one of these predictions is
+    made with ``probs=(0.025, 0.975)`` and also gains cover95, width95: len(cells) x n_sets."""
     res = {m: {"ls": [], "sf": [], "sn": [], "lml": [], "n_batches": []} for m in ("fixed", "learn")}
     if hmc:
         res["hmc"] = {"log_ls": [], "log_sf": [], "log_sn": [], "diverging": [], "seconds": []}
@@ -68,6 +75,16 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
         for m in ("learn", "hmc", "sparse", "sparse_hmc"):
             if m in res:
                 res[m].update(nlpd=[], rmse=[])
+                if calibration:
+                    res[m].update(cover95=[], width95=[])
+
+    def held(r, model, X_test, Y_test):  # the held-out figures of one fitted or sampled model
+        if not calibration:
+            pred = model.predict(X_test, Y_test)
+        else:
+            pred = model.predict(X_test, Y_test, probs=CALIBRATION_PROBS)
+            r["cover95"].append(pred.coverage(0.95)), r["width95"].append(pred.interval_width(0.95))
+        r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
     data = []
     for _, n, var in cells:
         X, Y, latent = ggp_amd.identification_data(n + holdout, n_sets, rng, noise_sd=float(np.sqrt(var)), uniform=uniform, latent=latent, **{
@@ -82,8 +99,7 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["lml"].append(fit.lml), r["n_batches"].append(fit.n_batches)
             if holdout and mode == "learn":
-                pred = fit.predict(X_test, Y_test)
-                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
+                held(r, fit, X_test, Y_test)
         if sparse:
             t0 = time.time()
             Xs = np.sort(X, 0)
@@ -93,8 +109,7 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
             r["ls"].append(fit.theta[:, 0]), r["sf"].append(np.sqrt(fit.theta[:, 1])), r["sn"].append(np.sqrt(fit.theta[:, 2]))
             r["elbo"].append(fit.elbo), r["seconds"].append(time.time() - t0)
             if holdout:
-                pred = fit.predict(X_test, Y_test)
-                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
+                held(r, fit, X_test, Y_test)
             if hmc:
                 post = fit.sample_nuts(hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed)
                 with np.errstate(invalid="ignore"):
@@ -102,28 +117,26 @@ def sweep(cells, n_sets, ls_upper, n_restarts, rng, latent, uniform, engine, see
                 r["ls"].append(mean[:, 0]), r["sf"].append(mean[:, 1]), r["sn"].append(mean[:, 2])
                 r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
                 if holdout:
-                    pred = post.predict(X_test, Y_test)
-                    r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
+                    held(r, post, X_test, Y_test)
         if hmc:
             post = ggp_amd.sample_exact_nuts_batch(X, Y, hmc["draws"], hmc["tune"], chains=hmc["chains"], seed=seed, engine=engine)
             mean, r = post.posterior_mean(), res["hmc"]
             r["log_ls"].append(mean[:, 0]), r["log_sf"].append(mean[:, 1]), r["log_sn"].append(mean[:, 2])
             r["diverging"].append(float(np.nanmean(post.stats[..., 4]))), r["seconds"].append(post.wall_clock_secs)
             if holdout:
-                pred = post.predict(X_test, Y_test)
-                r["nlpd"].append(pred.nlpd()), r["rmse"].append(pred.rmse(Y_test))
+                held(r, post, X_test, Y_test)
     return {m: {k: np.array(v) for k, v in r.items()} for m, r in res.items()}, data, latent
 
 
 def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n_sets=100, grid=50, n_noise=30, bimodal=False, seed=57,
-        engine=None, hmc=None, holdout=0, sparse=None):
+        engine=None, hmc=None, holdout=0, sparse=None, calibration=False):
     rng = np.random.default_rng(seed)
     out, summary = {}, {"sizes": list(sizes), "noise_vars": list(noise_vars), "n_sets": n_sets, "true": TRUE}
     t0 = time.time()
     size_res, size_data, latent = sweep([(n, n, 1.0) for n in sizes], n_sets, 1e3, 10, rng, None, not bimodal, engine, seed, hmc,
-                                        holdout, sparse)
+                                        holdout, sparse, calibration)
     noise_res, noise_data, latent = sweep([(v, n_noise, float(v)) for v in noise_vars], n_sets, 1e4, 5, rng, latent, not bimodal, engine,
-                                          seed, hmc, holdout, sparse)
+                                          seed, hmc, holdout, sparse, calibration)
     summary["fit_seconds"] = time.time() - t0
     for name, res in (("size", size_res), ("noise", noise_res)):
         for mode, r in res.items():
@@ -132,6 +145,9 @@ def run(sizes=(10, 15, 20, 25, 40, 60, 80, 100, 120), noise_vars=(1, 3, 6, 9), n
             if "nlpd" in r:  # held-out points: the cell's data sets averaged, the ML-II plug-in (noise learnt) beside the NUTS mixture
                 tag = "ml2" if mode == "learn" else mode  # (hmc, sparse, sparse_hmc: under their own names)
                 summary["%s_%s_nlpd" % (name, tag)], summary["%s_%s_rmse" % (name, tag)] = r["nlpd"].mean(1).tolist(), r["rmse"].mean(1).tolist()
+                if "cover95" in r:
+                    summary["%s_%s_cover95" % (name, tag)] = r["cover95"].mean(1).tolist()
+                    summary["%s_%s_width95" % (name, tag)] = r["width95"].mean(1).tolist()
             if mode == "hmc":  # the posterior means of the cell's data sets, averaged; beside ML-II's log of the mean fitted lengthscale
                 for k in ("log_ls", "log_sf", "log_sn"):
                     summary["%s_hmc_mean_%s" % (name, k)] = r[k].mean(1).tolist()
@@ -203,12 +219,16 @@ def main(argv=None, engine=None):
     ap.add_argument("--hmc_tune", type=int, default=500)
     ap.add_argument("--hmc_draws", type=int, default=500)
     ap.add_argument("--holdout", type=int, default=0, help="points per data set kept out of the fit and the sampling, and predicted")
+    ap.add_argument("--calibration", action="store_true", help="with --holdout: coverage and width of the central 95 %% interval")
     ap.add_argument("--sparse", type=int, default=0, help="also fit the collapsed sparse bound with this many inducing inputs (at most 64)")
     ap.add_argument("--sparse_steps", type=int, default=2000)
     args = ap.parse_args(argv)
+    if args.calibration and not args.holdout:
+        ap.error("--calibration needs --holdout K")
     hmc = {"chains": args.hmc_chains, "tune": args.hmc_tune, "draws": args.hmc_draws} if args.hmc else None
     out, summary = run(args.sizes, args.noise_vars, args.n_sets, args.grid, bimodal=args.bimodal, seed=args.seed, engine=engine, hmc=hmc,
-                       holdout=args.holdout, sparse={"M": args.sparse, "steps": args.sparse_steps} if args.sparse else None)
+                       holdout=args.holdout, sparse={"M": args.sparse, "steps": args.sparse_steps} if args.sparse else None,
+                       calibration=args.calibration)
     os.makedirs(args.out, exist_ok=True)
     base = os.path.join(args.out, "hyperparameter_identification")
     np.savez_compressed(base + ".npz", **out)

@@ -9,7 +9,7 @@ from .composite import (CO2_LOG_PRIOR_SD, CO2_SGPMC_PRIORS, CompositeBayesianSpa
 from .core import CollapsedBound, NotPositiveDefiniteError, SgpTimeoutError, shard_rows  # noqa: F401
 from . import datasets, experiment_tools  # noqa: F401
 from .exact_nuts import ExactNutsResult, chain_seed, sample_exact_nuts_batch  # noqa: F401
-from .exact_predict import ExactMixturePredictive, predict_exact_batch  # noqa: F401
+from .exact_predict import ExactMixturePredictive, mixture_quantiles, predict_exact_batch  # noqa: F401
 from .gp_shim import (BernoulliLikelihood, ExactMarginalLogLikelihood, GaussianLikelihood, InducingPointKernel, MaternKernel,  # noqa: F401
                       MultivariateNormal, PoissonLikelihood, RBFKernel, RobustMaxLikelihood, ScaleKernel, ZeroMean, settings)
 from .hmc import NUTS, SplitMix, Trace, sample_hmc, sample_nuts, sample_nuts_device  # noqa: F401

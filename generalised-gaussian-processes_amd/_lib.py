@@ -309,6 +309,16 @@ VFE_PREDICT_PROTOTYPES = {
 }
 VFE_PREDICT_MAX_T = 32768  # VP_MAXT
 
+# the companion library libsgp_mixture_hip.so (include/sgp_mixture.h): quantiles and the PIT of the mixture over the draws of a group
+_MQ = [_vp, _vp, _vp, _vp, _i64, _i64, _dp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+MIXTURE_LIB_PATH = os.path.join(HERE, "csrc", "libsgp_mixture_hip.so")
+MIXTURE_PROTOTYPES = {
+    "sgp_mixture_quantiles_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "sgp_mixture_quantiles": (_i32, _MQ),
+    "sgp_ctx_mixture_quantiles": (_i32, [_vp] + _MQ),
+}
+MIXTURE_MAX_Q, MIXTURE_P_MIN = 8, 1e-9  # MQ_MAXQ, MQ_PMIN
+
 # key -> (path, prototypes) of a companion library; _COMPANION_LIBS caches what has been loaded
 _COMPANION_TABLE = {
     "exact_nuts": (EXACT_NUTS_LIB_PATH, EXACT_NUTS_PROTOTYPES),
@@ -316,6 +326,7 @@ _COMPANION_TABLE = {
     "vfe_batch": (VFE_BATCH_LIB_PATH, VFE_BATCH_PROTOTYPES),
     "vfe_nuts": (VFE_NUTS_LIB_PATH, VFE_NUTS_PROTOTYPES),
     "vfe_predict": (VFE_PREDICT_LIB_PATH, VFE_PREDICT_PROTOTYPES),
+    "mixture": (MIXTURE_LIB_PATH, MIXTURE_PROTOTYPES),
 }
 _LIB = None
 _COMPANION_LIBS = {}
@@ -386,6 +397,11 @@ def load_vfe_nuts_library():
 def load_vfe_predict_library():
     """The batched sparse predictive's library (include/sgp_vfe_predict.h)."""
     return _load_companion("vfe_predict")
+
+
+def load_mixture_library():
+    """The mixture quantiles' library (include/sgp_mixture.h)."""
+    return _load_companion("mixture")
 
 
 def check(fn_name: str, status: int):

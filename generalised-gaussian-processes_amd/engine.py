@@ -977,6 +977,7 @@ class HipEngine:
     vfe_batch_lib = _companion_lib("vfe_batch", "the batched collapsed bound (include/sgp_vfe_batch.h)")
     vfe_nuts_lib = _companion_lib("vfe_nuts", "the batched sparse sampler (include/sgp_vfe_nuts.h)")
     vfe_predict_lib = _companion_lib("vfe_predict", "the batched sparse predictive (include/sgp_vfe_predict.h)")
+    mixture_lib = _companion_lib("mixture", "the mixture quantiles (include/sgp_mixture.h)")
     del _companion_lib
 
     @staticmethod
@@ -1151,6 +1152,52 @@ class HipEngine:
                                           ws.numel(), self._stream())
         _lib.check("sgp_exact_mixture_reduce", st)
         return {"mean": mm, "var": mv, "logpdf": lp, "mean_logpdf": mlp, "kept": kept}
+
+    @staticmethod
+    def _mixture_quantiles_intake(device, mean, var, info, offsets, probs, Ytest=None):
+        """What ``mixture_quantiles`` refuses before it allocates anything: returns (P, T, G, offsets as int64 numpy, probs as a C array
+        of Q doubles).  It runs on CPU tensors as well."""
+        _chk(device, mean, "mean"), _chk(device, var, "var")
+        if mean.dim() != 2 or var.shape != mean.shape or not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or \
+                info.device != device or not info.is_contiguous() or info.numel() != mean.shape[0]:
+            raise ValueError("mean and var must be P x T and info P contiguous int32 on %s" % (device,))
+        P, T = mean.shape
+        off = np.asarray(offsets)
+        if off.dtype.kind not in "iu" or off.ndim != 1:
+            raise ValueError("offsets must be a sequence of integers")
+        off = off.astype(np.int64)
+        G = off.size - 1
+        if G < 1 or off[0] != 0 or off[-1] != P or np.any(np.diff(off) < 0):
+            raise ValueError("offsets must be non-decreasing from 0 to %d (got %d entries)" % (P, off.size))
+        pr = np.asarray(probs, dtype=np.float64).reshape(-1)
+        if not 1 <= pr.size <= _lib.MIXTURE_MAX_Q or not np.all((pr >= _lib.MIXTURE_P_MIN) & (pr <= 1.0 - _lib.MIXTURE_P_MIN)):
+            raise ValueError("probs must be 1 to %d probabilities in [%g, 1 - %g] (got %s)"
+                             % (_lib.MIXTURE_MAX_Q, _lib.MIXTURE_P_MIN, _lib.MIXTURE_P_MIN, pr.tolist()))
+        if Ytest is not None:
+            _chk(device, Ytest, "Ytest")
+            if tuple(Ytest.shape) != (G, T):
+                raise ValueError("Ytest must be %d x %d (got %s)" % (G, T, tuple(Ytest.shape)))
+        return P, T, G, off, (C.c_double * pr.size)(*pr.tolist())
+
+    def mixture_quantiles(self, mean, var, info, offsets, probs, Ytest=None, want_iters=False):
+        """Quantiles and the PIT of the mixture over the draws of each group in ONE launch (include/sgp_mixture.h:
+        sgp_mixture_quantiles), on what ``exact_mixture`` takes: rows [offsets[g], offsets[g + 1]) of mean / var (P x T, device) are the
+        draws of group g; draws with info != 0 are left out.  ``probs``: 1 to 8 host probabilities in [1e-9, 1 - 1e-9].  Returns a
+        dict of device tensors: quantiles [G, Q, T], pit [G, T] = the mixture CDF at ``Ytest`` (G x T; None without), iters [G, T]
+        int32 with ``want_iters`` (None without).  A group with no draw left is NaN.  Nothing is synchronised."""
+        _, T, G, off, pr = self._mixture_quantiles_intake(self.device, mean, var, info, offsets, probs, Ytest)
+        Q = len(pr)
+        off_d = torch.as_tensor(off).to(self.device)
+        quant = self.empty(G, Q, T)
+        pit = self.empty(G, T) if Ytest is not None else None
+        iters = torch.empty(G, T, dtype=torch.int32, device=self.device) if want_iters else None
+        lib = self.mixture_lib
+        ws = self._workspace("mixture_quantiles", lib.sgp_mixture_quantiles_workspace_bytes(G, T, Q))
+        st = lib.sgp_ctx_mixture_quantiles(self._c(), self._ptr(mean), self._ptr(var), self._ptr(info), self._ptr(off_d), G, T, pr, Q,
+                                           self._ptr(Ytest), self._ptr(quant), self._ptr(pit), self._ptr(iters), self._ptr(ws),
+                                           ws.numel(), self._stream())
+        _lib.check("sgp_mixture_quantiles", st)
+        return {"quantiles": quant, "pit": pit, "iters": iters}
 
     def _launch_budget(self, budget: int, lib, occupancy: str, size: int, C: int, kernel) -> int:
         """``budget`` divided by the number of waves of workgroups C chains make on this device (chains per CU from the library's

@@ -145,12 +145,13 @@ class NutsBatchResult:
 class ExactNutsResult(NutsBatchResult):
     """``sample_exact_nuts_batch``'s result."""
 
-    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True):
-        """The mixture predictive (``exact_predict.predict_exact_batch``) over every ``thin``-th draw of every chain of each data set."""
+    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True, probs=None):
+        """The mixture predictive (``exact_predict.predict_exact_batch``) over every ``thin``-th draw of every chain of each data set;
+        ``probs``: the mixture's quantiles and PIT as well."""
         draws = self._thinned(thin, ("X", "Y"), "predict_exact_batch")
         from .exact_predict import predict_exact_batch
         return predict_exact_batch(self.X, self.Y, draws, X_test, Y_test, kernel=self.kernel, jitter=self.jitter or 0.0,
-                                   pred_noise=pred_noise, engine=self.engine)
+                                   pred_noise=pred_noise, engine=self.engine, probs=probs)
 
 
 def _trace(samples, stats, seconds, evaluations, wall):

@@ -85,14 +85,14 @@ class Ml2Result:
     kernel: Optional[str] = None
     engine: object = None
 
-    def predict(self, X_test, Y_test=None, pred_noise=True):
+    def predict(self, X_test, Y_test=None, pred_noise=True, probs=None):
         """The plug-in predictive at ``theta`` (``exact_predict.ExactMixturePredictive`` with S = 1; theta is constrained already: no
         exp, no noise floor)."""
         if self.X is None or self.Y is None or self.kernel is None:
             raise ValueError("this result does not carry the data it was fitted to (X, Y, kernel)")
         from .exact_predict import predict_theta_batch
         return predict_theta_batch(self.X, self.Y, self.theta[:, None, :], X_test, Y_test, kernel=self.kernel, pred_noise=pred_noise,
-                                   engine=self.engine)
+                                   engine=self.engine, probs=probs)
 
 
 MEMORY, MAX_ITER, PGTOL, FTOL, ARMIJO = 10, 200, 1e-5, 2.2e-9, 1e-4  # FTOL: scipy's factr = 1e7 times 2.2e-16

@@ -103,14 +103,15 @@ class SgprBatchResult:
         m.likelihood.noise = float(self.theta[b, d + 1])
         return m
 
-    def predict(self, X_test, Y_test=None, pred_noise=True):
+    def predict(self, X_test, Y_test=None, pred_noise=True, probs=None):
         """The plug-in predictive at the fitted ``theta`` and ``Z`` of every data set (``sgpr_predict.SgprMixturePredictive`` with
         S = 1; theta is constrained already: no exp) -- ``Ml2Result.predict``'s counterpart."""
         if self.X is None or self.Y is None:
             raise ValueError("this result does not carry the data")
         from .sgpr_predict import predict_sgpr_theta_batch
         return predict_sgpr_theta_batch(self.X if self.X.shape[0] > 1 else self.X[0], self.Y, self.Z, self.theta[:, None, :], X_test,
-                                        Y_test, kernel=self.kernel, jitter=self.jitter, pred_noise=pred_noise, engine=self.engine)
+                                        Y_test, kernel=self.kernel, jitter=self.jitter, pred_noise=pred_noise, engine=self.engine,
+                                        probs=probs)
 
     def sample_nuts(self, n_samples: int, tune: int, chains: int = 1, seed=None, **opts):
         """NUTS over theta for every data set at its fitted Z -- the reference's ``train_fixed_model`` protocol (ML-II for Z, then NUTS

@@ -34,13 +34,14 @@ class SgprNutsResult(NutsBatchResult):
     """``sample_sgpr_nuts_batch``'s result."""
     Z: Optional[np.ndarray] = None       # M x d or B x M x d
 
-    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True):
+    def predict(self, X_test, Y_test=None, thin=1, pred_noise=True, probs=None):
         """The mixture predictive (``sgpr_predict.predict_sgpr_batch``) over every ``thin``-th draw of every chain of each data set, at
-        the inducing inputs, kernel and jitter the draws were sampled with."""
+        the inducing inputs, kernel and jitter the draws were sampled with; ``probs``: the mixture's quantiles and PIT as well."""
         draws = self._thinned(thin, ("X", "Y", "Z"), "predict_sgpr_batch")
         from .sgpr_predict import predict_sgpr_batch
         return predict_sgpr_batch(self.X, self.Y, self.Z, draws, X_test, Y_test, kernel=self.kernel,
-                                  jitter=1e-6 if self.jitter is None else self.jitter, pred_noise=pred_noise, engine=self.engine)
+                                  jitter=1e-6 if self.jitter is None else self.jitter, pred_noise=pred_noise, engine=self.engine,
+                                  probs=probs)
 
     def model(self, b: int):
         """A ``BayesianSparseGPR_HMC`` over data set b with its inducing inputs Z_b: ``mixture_posterior_predictive(model, X_test,

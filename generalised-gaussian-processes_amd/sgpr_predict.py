@@ -25,12 +25,13 @@ class SgprMixturePredictive(ExactMixturePredictive):
 
 
 def predict_sgpr_theta_batch(X, Y, Z, theta, X_test, Y_test=None, kernel="rbf", jitter=1e-6, pred_noise=True,
-                             engine=None) -> SgprMixturePredictive:
-    """The mixture predictive at constrained rows: ``theta`` is B x S x (d + 2), rows [ls_1..d | sf2 | s2], used as they are."""
+                             engine=None, probs=None) -> SgprMixturePredictive:
+    """The mixture predictive at constrained rows: ``theta`` is B x S x (d + 2), rows [ls_1..d | sf2 | s2], used as they are.
+    ``probs``: as in ``predict_exact_batch``."""
     def run(eng, data, th, Xt, idx):
         return eng.vfe_predict_batch(*data, th, Xt, ix=idx[0], iy=idx[1], iz=idx[2], ixs=idx[3], kernel=kernel, jitter=jitter,
                                      pred_noise=pred_noise, want_bound=True)
-    return _mixture_frame(SgprMixturePredictive, run, X, Y, Z, (MAX_N, MAX_D, MAX_M), theta, X_test, Y_test, kernel, engine)
+    return _mixture_frame(SgprMixturePredictive, run, X, Y, Z, (MAX_N, MAX_D, MAX_M), theta, X_test, Y_test, kernel, engine, probs)
 
 
 def constrain_sgpr_samples(samples):
@@ -44,7 +45,7 @@ def constrain_sgpr_samples(samples):
 
 
 def predict_sgpr_batch(X, Y, Z, samples, X_test, Y_test=None, kernel="rbf", jitter=1e-6, pred_noise=True,
-                       engine=None) -> SgprMixturePredictive:
+                       engine=None, probs=None) -> SgprMixturePredictive:
     """The mixture predictive of B collapsed sparse GPs over S hyper-parameter draws each, on the device: one launch of the predictive
     kernel (B x S problems, one workgroup each), one of the mixture kernel, one host copy.
 
@@ -52,9 +53,10 @@ def predict_sgpr_batch(X, Y, Z, samples, X_test, Y_test=None, kernel="rbf", jitt
     B x T or None.  ``samples``: B x S x (d + 2) unconstrained positions [log ls | log sig_f | log sig_n] (``SgprNutsResult.samples``
     flattened over the chains); theta = [exp, exp^2, exp^2], with no noise floor; ``jitter`` goes on K_uu, as in the sampler.  A row
     with a NaN (a chain that had no start) fails the kernel's test of theta and is left out of the mixture (``info``, ``kept``), as is
-    a draw whose K_uu or B is not numerically positive definite."""
+    a draw whose K_uu or B is not numerically positive definite.  ``probs``: the mixture's quantiles and PIT, as in
+    ``predict_exact_batch`` (one more launch; none without)."""
     samples = _host(samples)
     if samples.ndim == 2:
         samples = samples[None]
     return predict_sgpr_theta_batch(X, Y, Z, constrain_sgpr_samples(samples), X_test, Y_test, kernel=kernel, jitter=jitter,
-                                    pred_noise=pred_noise, engine=engine)
+                                    pred_noise=pred_noise, engine=engine, probs=probs)
