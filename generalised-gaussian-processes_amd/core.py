@@ -126,6 +126,33 @@ class GuardState:
             self.open = not (self.predicted < 0.5 * tol)
 
 
+class Attempt:
+    """What ONE attempt of an evaluation produced: the tier, the result buffer (`buf`, with `out` and the status word `info` inside it), what
+    pass 1 and the tail left on the device (adjoints: None for a value-only attempt) and, once `_fetch` has run, the host's view -- `host`
+    (the copy), `o` (out as floats), `status` (the status word), the packed gradient behind `head`.  `factored`: the route of pass 2 -- L^-T Cw L^-1
+    applied factor by factor (whitened order), else the explicit Phibar with or without its trailing word `Phibar_lo` (the extended order forms
+    its Phibar FROM a core and still takes this route).  `complete`: everything the caller needs is on the host, so the walk can come back to
+    the attempt; `need`: the tier its own estimate names, once `_verdict` has read it."""
+
+    __slots__ = ("tier", "buf", "out", "info", "packed", "Kuu", "linv", "Phibar", "bbar", "Kuubar", "Cw", "Phibar_lo", "factored", "kfu", "kfu_f16",
+                 "t_keep", "factors", "reported", "host", "o", "status", "head", "complete", "need")
+
+    def __init__(self, tier, res, head, packed, Kuu, linv, kfu=None, kfu_f16=None, t_keep=None, factored=False):
+        get = res.get   # (what engine.bound returned: the adjoints and factors it was asked for)
+        self.tier, self.buf, self.out, self.info, self.head = tier, res["buf"], res["out"], res["info"], head
+        self.packed, self.Kuu, self.linv, self.kfu, self.kfu_f16, self.t_keep = packed, Kuu, linv, kfu, kfu_f16, t_keep
+        self.Phibar, self.bbar, self.Kuubar, self.Cw, self.factors = get("Phibar"), get("bbar"), get("Kuubar"), get("Cw"), get("factors")
+        self.Phibar_lo = self.host = self.o = self.status = self.need = None
+        self.factored, self.reported, self.complete = factored, False, False
+
+
+class Plan:
+    """What one evaluation settles before its first attempt: see `CollapsedBound._plan`."""
+
+    __slots__ = ("M", "with_grad", "want_gz", "want_factors", "strict", "want_lo", "guard", "reach", "ext_ok", "tier", "nh", "lo_slots",
+                 "extra", "early", "lo_check")
+
+
 WHITENED_ROWS_MIN_WORK = 1 << 26
 
 
@@ -263,46 +290,47 @@ class CollapsedBound:
             self.n_collectives += 1
         return stats
 
-    def _fetch(self, res, upto=None):
-        """The one host round trip of an evaluation: a single device-to-host copy of the result buffer ([out | status
-        word | whatever the caller appended], see ``HipEngine.result_buffer``) -- no cast / concatenate launches."""
-        buf = res["buf"] if upto is None else res["buf"][:upto]
-        host = buf.detach().to("cpu")
-        o, info = self.engine.read_result(host)
-        if info < 0:  # not a pivot index: the evaluation itself failed (time-out), with raise_on_fail or without
+    def _fetch(self, att, plan, full=True):
+        """The one host round trip of an evaluation: a single device-to-host copy of the attempt's result buffer ([out | status word | ... |
+        packed gradient], see ``HipEngine.result_buffer``) -- no cast / concatenate launches.  full: with the gradient pass 2 wrote."""
+        # (with the correction's slots the whole buffer: they sit at its end)
+        upto = att.head if not (full and plan.with_grad) else (None if plan.lo_slots else att.head + plan.nh + 1)
+        att.host = host = (att.buf if upto is None else att.buf[:upto]).detach().to("cpu")
+        att.o, att.status = self.engine.read_result(host)
+        if att.status < 0:  # not a pivot index: the evaluation itself failed (time-out), with raise_on_fail or without
             raise SgpTimeoutError()
-        return o, info, host
+        att.complete = (full or not plan.with_grad) and not plan.want_factors
+        return att
+
+    @staticmethod
+    def _failed(info, raise_on_fail=True):
+        """What value / value_and_grad / factors answer to a non-positive Cholesky pivot: the error, or (NaN, the pivot's index)."""
+        if raise_on_fail:
+            raise NotPositiveDefiniteError(info)
+        return float("nan"), {"info": info}
 
     def _prep_Z(self, Z):
         if Z.dim() == 1:
             Z = Z[:, None]
         return Z.detach().to(dtype=torch.float64, device=self.engine.device).contiguous()
 
-    def _kfu_for(self, M):
-        e = self.engine
-        if not hasattr(e, "kfu_buffer"):
-            return None
-        n_local = int(self.X.shape[0])
+    def _kept_block(self, M, name, make, bytes_per):
+        """The block of the local shard's K'_fu shape that the bound keeps in `name` (None: not with this engine, or beyond the budget)."""
+        e, n_local = self.engine, int(self.X.shape[0])
         need = ((max(n_local, 1) + 255) // 256 * 256) * ((M + 127) // 128 * 128)
-        if need * 8 > self.kfu_budget_bytes:
+        if not hasattr(e, make) or need * bytes_per > self.kfu_budget_bytes:
             return None
-        if self._kfu is None or self._kfu.numel() < need:
-            self._kfu = e.kfu_buffer(n_local, M)
-        return self._kfu
+        if getattr(self, name) is None or getattr(self, name).numel() < need:
+            setattr(self, name, getattr(e, make)(n_local, M))
+        return getattr(self, name)
+
+    def _kfu_for(self, M):
+        return self._kept_block(M, "_kfu", "kfu_buffer", 8)
 
     def _kfu_f16_for(self, M):
         """The fp16 image of K'_fu beside the fp64 block (the extended order's trailing-word product reads it; written by the assembly
         kernel, which spares sgp_suffstats_bwd_lo a conversion pass over the fp64 block: 2.0 of 4.6 ms at C5)."""
-        e = self.engine
-        if not hasattr(e, "kfu_f16_buffer"):
-            return None
-        n_local = int(self.X.shape[0])
-        need = ((max(n_local, 1) + 255) // 256 * 256) * ((M + 127) // 128 * 128)
-        if need * 10 > self.kfu_budget_bytes:
-            return None
-        if self._kfu_f16 is None or self._kfu_f16.numel() < need:
-            self._kfu_f16 = e.kfu_f16_buffer(n_local, M)
-        return self._kfu_f16
+        return self._kept_block(M, "_kfu_f16", "kfu_f16_buffer", 10)
 
     # ------------------------------------------------------------------ single-launch path (small problems)
     def _small_ok(self, M, want_gz=False, sf2=1.0):
@@ -360,23 +388,14 @@ class CollapsedBound:
 
     def _trace_buf(self):
         if getattr(self, "_trace", None) is None:  # tr(Kuu^-1) + its scratch: one buffer per bound, reused by every evaluation
-            e = self.engine
-            self._trace = e.empty(e.lib.sgp_kuu_inverse_trace_len() if hasattr(e, "lib") else 2)
+            self._trace = self.engine.empty(self.engine.lib.sgp_kuu_inverse_trace_len() if hasattr(self.engine, "lib") else 2)
         return self._trace
 
-    # -- compatibility of the counters' old names (tests, tools)
-    @property
-    def _prefer_whitened(self):
-        return self.guard.open
-
-    @_prefer_whitened.setter
-    def _prefer_whitened(self, v):
-        self.guard.open = bool(v)
+    _prefer_whitened = property(lambda self: self.guard.open, lambda self, v: setattr(self.guard, "open", bool(v)))  # `guard.open` under its old name
 
     def _guard_on(self, M):
         """The guard watches this bound: form="auto" above the size where "auto" means whitened anyway, a tolerance, an engine that reports."""
-        return (self.form == "auto" and self.streaming_tol > 0.0 and hasattr(self.engine, "streaming_error_report")
-                and not self._whitened(M))
+        return self.form == "auto" and self.streaming_tol > 0.0 and hasattr(self.engine, "streaming_error_report") and not self._whitened(M)
 
     def _extended_ok(self, M):
         """The extended order exists for this bound (a rank-invariant statement: the shard size is the largest one of the job)."""
@@ -392,293 +411,283 @@ class CollapsedBound:
                 and e.bwd_lo_supported(self._rows_for_form, int(M), self.d, self.kernel)
                 and ((self._rows_for_form + 255) // 256 * 256) * ((int(M) + 127) // 128 * 128) * 8 <= self.kfu_budget_bytes)
 
-    def _lo_correction_small(self, host, head, nh, lo_slots):
-        """The a-posteriori check of the extended order's gradient: the trailing word's correction [d lengthscales | sf2] (tail of the
-        buffer) against the gradient it went into, in the parity suite's metric -- lengthscales against their largest component,
-        the amplitude against max(1, |g_sf2|)."""
-        g = host[head:head + nh + 1].tolist()
-        dl = host[host.numel() - lo_slots:].tolist()
-        if any(v != v for v in dl):   # NaN: the product's inputs were beyond its fp16 format (an inducing point > 128 lengthscales out) -- no correction was added
-            self.last_lo_correction = float("inf")
-            return False
-        self.last_lo_correction = max(max(abs(v) for v in dl[:nh]) / max(1.0, max(abs(v) for v in g[:nh])), abs(dl[nh]) / max(1.0, abs(g[nh])))
-        return self.last_lo_correction <= self.extended_lo_max_correction
+    def _plan(self, M, d, with_grad=False, want_gz=False, want_factors=False, grad_reach=None, strict=False):
+        """Everything one evaluation settles before its first attempt.  All of it follows from replicated numbers: ranks plan alike."""
+        e, p = self.engine, Plan()
+        p.M, p.with_grad, p.want_gz, p.want_factors, p.strict = M, with_grad, want_gz, want_factors, strict
+        p.guard, p.ext_ok, p.want_lo = self._guard_on(M), self._extended_ok(M), grad_reach is None   # (the sampler mode takes tier 1's gradient as it is)
+        lo_ok = with_grad and self._bwd_lo_ok(M)
+        p.reach = self.extended_range
+        if with_grad:   # (how far the extended order's gradient holds 1e-6: further with both words of its double-double Phibar)
+            p.reach = float(grad_reach) if grad_reach is not None else (self.extended_grad_range_lo if lo_ok else self.extended_grad_range)
+        if p.guard:
+            p.tier = self.guard.start_tier(self.streaming_tol, p.reach, p.ext_ok)
+            if strict and p.tier == TIER_WHITENED:
+                # strict: the ACCEPTED tier is the one the evaluation's own exact estimate names.  The whitened order states only an upper
+                # bound -- whether it would be left for a lower tier was a matter of the guard's memory (ADVICE r5: the same theta accepted
+                # in tier 1 on a fresh bound and in tier 2 after some history).  So a strict evaluation starts at most in the highest tier
+                # that states its exact estimate, and reaches the whitened order only when that estimate sends it there.
+                p.tier = TIER_EXTENDED if p.ext_ok else TIER_STREAMING
+            if p.tier != TIER_STREAMING:
+                self.n_direct_whitened += 1
+        else:
+            p.tier = TIER_EXTENDED if self.form == "extended" else (TIER_WHITENED if self._whitened(M) else TIER_STREAMING)
+        p.nh = (e.hyper_len(self.kernel, d) if hasattr(e, "hyper_len") else d) if with_grad else 0
+        # (behind the packed gradient: d + 1 slots for the trailing word's correction, which decides whether the explicit pass 2 is trusted)
+        p.lo_slots = (p.nh + 1) if (p.guard and p.ext_ok and lo_ok) else 0
+        p.extra = p.nh + 1 + (M * d if want_gz else 0) + p.lo_slots if with_grad else 0
+        p.lo_check = bool(p.lo_slots) and p.want_lo   # an extended-order gradient is accepted by its trailing-word correction (`_verdict`)
+        if p.guard and with_grad and p.tier == TIER_EXTENDED and p.want_lo and self._lo_skip > 0:
+            # the trailing word's correction was too large a moment ago: the next few gradient evaluations go straight to the whitened order (no
+            # wasted attempt per leapfrog); the pause doubles with every rejection in a row (8, 16, 32) and ends with the first acceptance
+            self._lo_skip -= 1
+            p.tier = TIER_WHITENED
+        # Small shards: pass 2 is enqueued straight behind the tail and ONE copy at the very end brings back F, the status and the
+        # gradient -- a failed factorization or a guard repeat then costs a wasted pass 2, which is cheaper than idling the GPU for
+        # a host round trip on every leapfrog.  Big shards check first.  The rule is the job's (largest shard), not this rank's:
+        # ranks must issue the same collectives in the same order.
+        p.early = with_grad and self._rows_for_form * M >= self.early_check_min_work
+        return p
 
-    def _fixed_tier(self, M):
-        if self.form == "extended":
-            return TIER_EXTENDED
-        return TIER_WHITENED if self._whitened(M) else TIER_STREAMING
-
-    def _review(self, res, host, info, tier, reach, M, strict):
-        """What the evaluation's own numbers say: None = accept, or the tier to repeat it in.  Updates the guard's memory.
-        A failed factorization of K_uu (info in 1 .. M), a time-out or a refusal says nothing about the estimate: the state is left alone
-        and nothing is repeated.  A failed factorization of B (info > M) below the whitened order is the streaming order's own failure
-        mode -- W = L^-1 Phi L^-T so far off that I + W / s2 is not positive definite (l = 20, sig_n = 0.01: profiles/r04_theta_sweep_streaming.jsonl)
-        -- and the estimate, which needs K_uu's factor and Phi only, is valid: it is reviewed like any other."""
-        if not res.get("reported") or (info != 0 and not (info > M and tier < TIER_WHITENED)):
-            return None
+    def _kuu_chain(self, Z, ls, sf2, result, trace, factor=True, side=None):
+        """(K_uu, L^-1) by engine.kuu + engine.kuu_factor (factor=False: K_uu alone, the tail factors it), on the calling stream -- or, `side`
+        (`_side_state`), on the side stream into the bound's buffers: the caller puts the main stream behind `ready` before the chain is read."""
         e = self.engine
-        est, ub = e.read_estimate(host), e.read_bound(host)
-        tol, ext_ok = self.streaming_tol, self._extended_ok(M)
-        self.last_estimate = est
-        if tier == TIER_WHITENED:
-            # (only the upper bound is known here: nothing this order states can send the evaluation DOWN -- a strict evaluation never
-            # starts in it, see _evaluate, so whatever is accepted here was sent up by a lower tier's exact estimate)
-            self.guard.note_bound(ub, tol)
-            return None
-        need = required_tier(est, tol, reach, ext_ok)
-        self.guard.note_exact(est, ub, tol)
-        if need > tier:
-            self.guard.open = True
-            return need
-        if info != 0:  # B failed although the estimate is inside this tier's reach: the next tier up, if there is one
-            return tier + 1 if (tier + 1 < TIER_WHITENED and ext_ok) else TIER_WHITENED
-        if strict and need < tier:
-            return need
-        return None
+        if side is None:
+            Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
+            return Kuu, (e.kuu_factor(Kuu, info=result[2], trace_out=trace)[0] if factor else None)
+        stream, (z_ready, ready), (Kuu, linv) = side
+        z_ready.record(torch.cuda.current_stream(e.device))  # Z is materialised on the main stream
+        stream.wait_event(z_ready)
+        # (the side stream's accesses to the result buffer and to Kuubar end before events the main stream waits for ahead of its
+        # own last use: no record_stream -- the allocator's per-block event bookkeeping costs the host ~25 us per evaluation)
+        e.kuu(Z, ls, sf2, self.jitter, self.kernel, out=Kuu, stream=stream)
+        e.kuu_factor(Kuu, info=result[2], trace_out=trace, out=linv, stream=stream)  # the evaluation's status word starts as the Kuu status
+        ready.record(stream)
+        return Kuu, linv
 
-    def _forward(self, Z, ls, sf2, s2, with_adjoints, want_factors=False, extra=0, tier=TIER_STREAMING, report=False, want_lo=True):
-        """One attempt in the given tier: pass 1, the exchange, the tail -- everything enqueued, nothing read back.
-        report: also the streaming-order estimate / bound into the result buffer (sgp_streaming_error_report)."""
-        e = self.engine
-        M = int(Z.shape[0])
-        result = e.result_buffer(extra)  # (buf, out, info): everything the host reads back, one allocation
-        if tier == TIER_EXTENDED:
-            # the extended streaming order: the whitened statistics from ONE integer-core contraction (39 digit pairs, double-double fold)
-            # and a double-double triple product; pass 2 from the explicit Phibar on the fp64 K'_fu kept here
-            self.n_extended += 1
-            Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
-            linv, _ = e.kuu_factor(Kuu, info=result[2], trace_out=self._trace_buf() if report else None)
-            kfu = self._kfu_for(M) if with_adjoints else None
-            diag = None
-            if report:
-                if self._phi_diag is None or self._phi_diag.numel() < M:
-                    self._phi_diag = e.empty(M)
-                diag = self._phi_diag
-            dd = with_adjoints and self.extended_dd_phibar and hasattr(e, "phibar_dd")
-            lo = dd and want_lo and kfu is not None and self._bwd_lo_ok(M)   # (not for the sampler mode: it takes this order's gradient as it is)
-            kfu_f16 = self._kfu_f16_for(M) if lo else None
-            packed = e.suffstats_extended(self.X, self.y, Z, ls, sf2, linv, self.kernel, kfu=kfu, level=self.extended_level,
-                                          **({"phi_diag": diag} if diag is not None else {}), **({"kfu_f16": kfu_f16} if kfu_f16 is not None else {}))
-            self._allreduce_stats(packed, M)
-            # pass 2 of this order takes the explicit Phibar = L^-T C L^-1 / (2 s2); formed by two fp64 products its own rounding
-            # (eps |L^-T| |C| |L^-1| >> eps |Phibar|) is what limits the gradients -- formed in double-double from the whitened core C the
-            # bound returns they are 5-15 x closer (tests/studies/explicit_phibar_pass2.py; +1.3 ms at M = 1024)
-            res = e.bound(Kuu, packed, s2, self.N, with_adjoints=with_adjoints, want_factors=want_factors, kuu_linv=linv,
-                          result=result, whitened=True, **({"want_cw": True} if dd else {}))
-            if dd:
-                # ... and 35-700 x closer with the trailing word applied as well: an fp16 product K' Phibar_lo beside the fp64 one (_pass2)
-                res["Phibar"], res["Phibar_lo"] = e.phibar_dd(res["Cw"], linv, s2, want_lo=lo)
-                res["Cw"] = None   # (pass 2 of this order is the explicit one: _pass2 takes the factored route when a core is handed on)
-            if report:
-                self._allreduce(diag[:M])  # (ranks hold the diagonal of their own shard's Phi)
-                e.streaming_error_report(diag, 1, self._trace_buf(), sf2, s2, self.N, M, result)
-                res["reported"] = True
-            res.update(packed=packed, kfu=kfu, kfu_f16=kfu_f16, t_keep=None, linv=linv)
-            return res
-        if tier == TIER_WHITENED:
-            # PyMC3 op order: chol(Kuu) first, then A = L^-1 K_uf, W = A A^T (one stream; these shards are small)
-            Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
-            rep = report and self.kernel != "composite"
-            linv, _ = e.kuu_factor(Kuu, info=result[2], trace_out=self._trace_buf() if rep else None)
-            # with adjoints: also the whitened core Cw of Phibar, so that pass 2 applies L^-T Cw L^-1 factor by factor
-            factored = with_adjoints and self.factored_adjoint and hasattr(e, "suffstats_bwd_factored")
-            t_keep = None
-            if whitened_rows_layout(e, self.kernel, int(self.X.shape[0]), M, self.whitened_rows_min_work):
-                # a large shard (the streaming guard's repeats at 10^6 rows): the streaming layout; T = K'_fu L^-T stays for pass 2
-                t_keep = self._kfu_for(M) if factored else None
-                packed = e.suffstats_whitened_rows(self.X, self.y, Z, ls, sf2, linv, self.kernel, t_out=t_keep)
-            else:
-                packed = e.suffstats_whitened(self.X, self.y, Z, ls, sf2, linv, self.kernel)
-            self._allreduce_stats(packed, M)
-            kw = {"want_cw": True} if factored else {}
-            res = e.bound(Kuu, packed, s2, self.N, with_adjoints=with_adjoints, want_factors=want_factors, kuu_linv=linv,
-                          result=result, whitened=True, **kw)
-            if rep:
-                e.streaming_error_report(None, 1, self._trace_buf(), sf2, s2, self.N, M, result)
-                res["reported"] = True
-            res.update(packed=packed, kfu=None, t_keep=t_keep, linv=linv)
-            return res
-        kfu = self._kfu_for(M) if with_adjoints else None
-        gate = None
-        guard = report
-        trace = self._trace_buf() if guard and hasattr(e, "kuu_factor") else None
+    def _report(self, att, diag, stride, sf2, s2, M):   # the streaming-order estimate and its bound into the attempt's result buffer
+        self.engine.streaming_error_report(diag, stride, self._trace_buf(), sf2, s2, self.N, M, (att.buf, att.out, att.info))
+        att.reported = True
+
+    def _attempt_streaming(self, Z, ls, sf2, s2, plan):
+        """An attempt in tier 0: pass 1, the exchange, the tail -- everything enqueued, nothing read back (as in every tier)."""
+        e, M = self.engine, plan.M
+        result = e.result_buffer(plan.extra)  # (buf, out, info): everything the host reads back, one allocation
+        kfu = self._kfu_for(M) if plan.with_grad else None
+        factor = hasattr(e, "kuu_factor")
+        trace = self._trace_buf() if plan.guard and factor else None
         # a second stream only pays once pass 1 is long enough to hide the Kuu chain under it (C3-sized and up; at C1 / C2 sizes
         # the hand-over costs more than the 0.1 ms it could hide)
-        overlap = (self.overlap_tail and hasattr(e, "kuu_factor") and e.device.type == "cuda"
-                   and int(self.X.shape[0]) * M >= self.overlap_min_work)
-        if overlap:
+        side = gate = None
+        if self.overlap_tail and factor and e.device.type == "cuda" and int(self.X.shape[0]) * M >= self.overlap_min_work:
             # chol(Kuu), its inverse, the conditioning gate and tr(Kuu^-1) depend on (Z, theta) only: engine.kuu + engine.kuu_factor, SIX
             # launches since round 5 (the factorization's launch forms L^-1 itself), on a side stream beside pass 1.  The calling thread
             # enqueues them first (~25 us; through round 4 the chain was ~50 launches, replayed from a hipGraph by a helper thread whose
             # wake-up alone cost 70 us: profiles/r05_v2_c3_timeline.txt), into buffers the bound keeps (no allocation, no stream
             # bookkeeping per evaluation: the previous evaluation's readers are ahead of `z_ready` in the main stream's order).
-            main = torch.cuda.current_stream(e.device)
-            side, (z_ready, ready), (Kuu, linv) = self._side_state(M)
-            z_ready.record(main)  # Z is materialised on the main stream
-            side.wait_event(z_ready)
-            # (the side stream's accesses to the result buffer and to Kuubar end before events the main stream waits for ahead of its
-            # own last use: no record_stream -- the allocator's per-block event bookkeeping costs the host ~25 us per evaluation)
-            e.kuu(Z, ls, sf2, self.jitter, self.kernel, out=Kuu, stream=side)
-            e.kuu_factor(Kuu, info=result[2], trace_out=trace, out=linv, stream=side)  # the evaluation's status word starts as the Kuu status
-            ready.record(side)
+            side = self._side_state(M)
+            Kuu, linv = self._kuu_chain(Z, ls, sf2, result, trace, side=side)
             # Big shards contract on the integer matrix cores, beside which nothing co-schedules: the contraction is gated on the
             # chain's end, so the chain runs beside kernel assembly (only where assembly outlasts the chain -- 2.0 ms vs 0.6 at
             # N = 1M, M = 1024, but 0.3 vs 0.6 at an eighth of it, where gating costs 0.1 ms: rows >= 300 M) ... and only where the
             # integer cores will actually contract (the library's own rule for this engine's context)
             if (hasattr(e, "would_use_i8") and self.kernel != "composite" and int(self.X.shape[0]) >= 300 * M
                     and e.would_use_i8(int(self.X.shape[0]), M)):
-                gate = ready
+                gate = side[1][1]
         try:
             packed = e.suffstats(self.X, self.y, Z, ls, sf2, self.kernel, kfu=kfu, **({"gate": gate} if gate is not None else {}))
             self._allreduce_stats(packed, M)
         finally:
             # the side stream writes `result`, the trace buffer and (Kuu, L^-1) with no record_stream: the main stream must be behind
             # `ready` before any of them can go back to its allocator pool -- also when pass 1 or the exchange raises (ADVICE r5)
-            if overlap:
-                main.wait_event(ready)
-        if overlap:
-            res = e.bound(Kuu, packed, s2, self.N, with_adjoints=with_adjoints, want_factors=want_factors, kuu_linv=linv,
-                          result=result)
-        elif guard and hasattr(e, "kuu_factor"):
-            Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
-            linv, _ = e.kuu_factor(Kuu, info=result[2], trace_out=trace)
-            res = e.bound(Kuu, packed, s2, self.N, with_adjoints=with_adjoints, want_factors=want_factors, kuu_linv=linv,
-                          result=result)
-        else:
-            Kuu = e.kuu(Z, ls, sf2, self.jitter, self.kernel)
-            res = e.bound(Kuu, packed, s2, self.N, with_adjoints=with_adjoints, want_factors=want_factors, result=result)
-        if guard and trace is not None:
-            e.streaming_error_report(packed, M + 1, trace, sf2, s2, self.N, M, result)
-            res["reported"] = True
-        res["packed"] = packed
-        res["kfu"] = kfu
-        return res
+            if side is not None:
+                torch.cuda.current_stream(e.device).wait_event(side[1][1])
+        if side is None:   # one stream: the chain behind pass 1 (without a guard: K_uu alone, the tail factors it itself)
+            Kuu, linv = self._kuu_chain(Z, ls, sf2, result, trace, factor=plan.guard and factor)
+        res = e.bound(Kuu, packed, s2, self.N, with_adjoints=plan.with_grad, want_factors=plan.want_factors, kuu_linv=linv, result=result)
+        att = Attempt(TIER_STREAMING, res, result[0].numel() - plan.extra, packed, Kuu, linv, kfu=kfu)
+        if trace is not None:
+            self._report(att, packed, M + 1, sf2, s2, M)
+        return att
 
-    def _pass2(self, res, Z, ls, sf2, s2, want_gz, g):
-        """Pass 2 on the local rows + the all-reduce of the gradients + the K_uu path, into the packed gradient slice `g`."""
-        e = self.engine
-        # kappabar = dF/dkappa = -1 / (2 s2) needs nothing from the device (same value the tail writes to out)
-        if res.get("Cw") is not None:
-            # whitened order: Phibar's cond(K_uu)-sized entries would cancel in Phibar K_uf -- its factors are applied instead
-            e.suffstats_bwd_factored(self.X, self.y, Z, ls, sf2, res["linv"], res["Cw"], s2, res["bbar"], -1.0 / (2.0 * float(s2)),
-                                     self.kernel, want_gz=want_gz, out=g,
-                                     **({"t_in": res["t_keep"]} if res.get("t_keep") is not None else {}))
+    def _attempt_extended(self, Z, ls, sf2, s2, plan):
+        """An attempt in tier 1, the extended streaming order: the whitened statistics from ONE integer-core contraction (39 digit pairs,
+        double-double fold) and a double-double triple product; pass 2 from the explicit Phibar on the fp64 K'_fu kept here."""
+        e, M, grad, report = self.engine, plan.M, plan.with_grad, plan.guard
+        result = e.result_buffer(plan.extra)
+        self.n_extended += 1
+        Kuu, linv = self._kuu_chain(Z, ls, sf2, result, self._trace_buf() if report else None)
+        kfu = self._kfu_for(M) if grad else None
+        if report and (self._phi_diag is None or self._phi_diag.numel() < M):
+            self._phi_diag = e.empty(M)
+        diag = self._phi_diag if report else None
+        dd = grad and self.extended_dd_phibar and hasattr(e, "phibar_dd")
+        lo = dd and plan.want_lo and kfu is not None and self._bwd_lo_ok(M)
+        kfu_f16 = self._kfu_f16_for(M) if lo else None
+        packed = e.suffstats_extended(self.X, self.y, Z, ls, sf2, linv, self.kernel, kfu=kfu, level=self.extended_level,
+                                      **({"phi_diag": diag} if diag is not None else {}), **({"kfu_f16": kfu_f16} if kfu_f16 is not None else {}))
+        self._allreduce_stats(packed, M)
+        # pass 2 of this order takes the explicit Phibar = L^-T C L^-1 / (2 s2); formed by two fp64 products its own rounding
+        # (eps |L^-T| |C| |L^-1| >> eps |Phibar|) is what limits the gradients -- formed in double-double from the whitened core C the
+        # bound returns they are 5-15 x closer (tests/studies/explicit_phibar_pass2.py; +1.3 ms at M = 1024)
+        res = e.bound(Kuu, packed, s2, self.N, with_adjoints=grad, want_factors=plan.want_factors, kuu_linv=linv,
+                      result=result, whitened=True, **({"want_cw": True} if dd else {}))
+        att = Attempt(TIER_EXTENDED, res, result[0].numel() - plan.extra, packed, Kuu, linv, kfu=kfu, kfu_f16=kfu_f16)
+        if dd:
+            # ... and 35-700 x closer with the trailing word applied as well: an fp16 product K' Phibar_lo beside the fp64 one (_pass2)
+            att.Phibar, att.Phibar_lo = e.phibar_dd(att.Cw, linv, s2, want_lo=lo)
+        if report:
+            self._allreduce(diag[:M])  # (ranks hold the diagonal of their own shard's Phi)
+            self._report(att, diag, 1, sf2, s2, M)
+        return att
+
+    def _attempt_whitened(self, Z, ls, sf2, s2, plan):
+        """An attempt in tier 2, PyMC3's op order: chol(Kuu) first, then A = L^-1 K_uf, W = A A^T (one stream; these shards are small)."""
+        e, M = self.engine, plan.M
+        result = e.result_buffer(plan.extra)
+        report = plan.guard and self.kernel != "composite"
+        Kuu, linv = self._kuu_chain(Z, ls, sf2, result, self._trace_buf() if report else None)
+        # with adjoints: also the whitened core Cw of Phibar, so that pass 2 applies L^-T Cw L^-1 factor by factor
+        factored = plan.with_grad and self.factored_adjoint and hasattr(e, "suffstats_bwd_factored")
+        t_keep = None
+        if whitened_rows_layout(e, self.kernel, int(self.X.shape[0]), M, self.whitened_rows_min_work):
+            # a large shard (the streaming guard's repeats at 10^6 rows): the streaming layout; T = K'_fu L^-T stays for pass 2
+            t_keep = self._kfu_for(M) if factored else None
+            packed = e.suffstats_whitened_rows(self.X, self.y, Z, ls, sf2, linv, self.kernel, t_out=t_keep)
         else:
-            e.suffstats_bwd(self.X, self.y, Z, ls, sf2, res["Phibar"], res["bbar"], -1.0 / (2.0 * float(s2)),
-                            self.kernel, want_gz=want_gz, out=g, kfu=res["kfu"])
-            if res.get("Phibar_lo") is not None:   # the extended order: the trailing word of its double-double Phibar (lengthscales, amplitude)
-                n_lo = int(res.get("lo_slots", 0))   # (the correction itself goes to the tail of `g`: all-reduced with it, read back with it)
-                e.suffstats_bwd_lo(self.X, self.y, Z, ls, sf2, res["Phibar_lo"], res["kfu"], g, self.kernel,
+            packed = e.suffstats_whitened(self.X, self.y, Z, ls, sf2, linv, self.kernel)
+        self._allreduce_stats(packed, M)
+        res = e.bound(Kuu, packed, s2, self.N, with_adjoints=plan.with_grad, want_factors=plan.want_factors, kuu_linv=linv,
+                      result=result, whitened=True, **({"want_cw": True} if factored else {}))
+        att = Attempt(TIER_WHITENED, res, result[0].numel() - plan.extra, packed, Kuu, linv, t_keep=t_keep, factored=res.get("Cw") is not None)
+        if report:
+            self._report(att, None, 1, sf2, s2, M)
+        return att
+
+    def _pass2(self, att, Z, ls, sf2, s2, plan):
+        """Pass 2 on the local rows + the all-reduce of the gradients + the K_uu path, into the packed gradient behind the attempt's head."""
+        e, g, n_lo = self.engine, att.buf[att.head:], plan.lo_slots
+        kappabar = -1.0 / (2.0 * float(s2))   # dF/dkappa needs nothing from the device (same value the tail writes to out)
+        if att.factored:
+            # whitened order: Phibar's cond(K_uu)-sized entries would cancel in Phibar K_uf -- its factors are applied instead
+            e.suffstats_bwd_factored(self.X, self.y, Z, ls, sf2, att.linv, att.Cw, s2, att.bbar, kappabar, self.kernel,
+                                     want_gz=plan.want_gz, out=g, **({"t_in": att.t_keep} if att.t_keep is not None else {}))
+        else:
+            e.suffstats_bwd(self.X, self.y, Z, ls, sf2, att.Phibar, att.bbar, kappabar, self.kernel, want_gz=plan.want_gz, out=g, kfu=att.kfu)
+            if att.Phibar_lo is not None:   # the extended order: the trailing word of its double-double Phibar (lengthscales, amplitude)
+                # (the correction itself goes to the tail of `g`: all-reduced with it, read back with it)
+                e.suffstats_bwd_lo(self.X, self.y, Z, ls, sf2, att.Phibar_lo, att.kfu, g, self.kernel,
                                    **({"delta": g[g.numel() - n_lo:]} if n_lo else {}),
-                                   **({"kfu_f16": res["kfu_f16"]} if res.get("kfu_f16") is not None else {}))
-        if int(res.get("lo_slots", 0)) and res.get("Phibar_lo") is None:
-            g[g.numel() - int(res["lo_slots"]):].zero_()   # (the correction's slots travel with g: nothing undefined into the all-reduce)
+                                   **({"kfu_f16": att.kfu_f16} if att.kfu_f16 is not None else {}))
+        if n_lo and att.Phibar_lo is None:
+            g[g.numel() - n_lo:].zero_()   # (the correction's slots travel with g: nothing undefined into the all-reduce)
         self._allreduce(g)
         # (measured and dropped, round 5: this launch pair on the side stream beside pass 2 -- it needs Kuubar only -- ends the evaluation no
         # earlier: pass 2 fills the chip and runs the 28 us longer that the side stream takes from it, profiles/r05_kuu_bwd_side_stream_c3_timeline.txt)
-        e.kuu_bwd(Z, ls, sf2, res["Kuubar"], g, self.kernel, want_gz=want_gz)
+        e.kuu_bwd(Z, ls, sf2, att.Kuubar, g, self.kernel, want_gz=plan.want_gz)
+
+    def _lo_correction_small(self, att, plan):
+        """The a-posteriori check of the extended order's gradient: the trailing word's correction [d lengthscales | sf2] (tail of the
+        buffer) against the gradient it went into, in the parity suite's metric -- lengthscales against their largest component,
+        the amplitude against max(1, |g_sf2|)."""
+        host, nh = att.host, plan.nh
+        g, dl = host[att.head:att.head + nh + 1].tolist(), host[host.numel() - plan.lo_slots:].tolist()
+        if any(v != v for v in dl):   # NaN: the product's inputs were beyond its fp16 format (an inducing point > 128 lengthscales out) -- no correction was added
+            self.last_lo_correction = float("inf")
+            return False
+        self.last_lo_correction = max(max(abs(v) for v in dl[:nh]) / max(1.0, max(abs(v) for v in g[:nh])), abs(dl[nh]) / max(1.0, abs(g[nh])))
+        return self.last_lo_correction <= self.extended_lo_max_correction
+
+    def _verdict(self, att, plan, may_go_down):
+        """What a fetched attempt's own numbers say: None = accept, or the tier to repeat the evaluation in.  The ONE place that reads the
+        estimate and the bound and updates what the guard remembers -- once per attempt, however often it is asked.
+        A failed factorization of K_uu (status in 1 .. M) or a refusal says nothing about the estimate: the state is left alone and
+        nothing is repeated.  A failed factorization of B (status > M) below the whitened order is the streaming order's own failure
+        mode -- W = L^-1 Phi L^-T so far off that I + W / s2 is not positive definite (l = 20, sig_n = 0.01: profiles/r04_theta_sweep_streaming.jsonl)
+        -- and the estimate, which needs K_uu's factor and Phi only, is valid: it is reviewed like any other."""
+        tier, status = att.tier, att.status
+        if plan.guard and att.reported and (status == 0 or (status > plan.M and tier < TIER_WHITENED)):
+            if att.need is None:
+                e, tol = self.engine, self.streaming_tol
+                est, ub = e.read_estimate(att.host), e.read_bound(att.host)
+                self.last_estimate = est
+                if tier == TIER_WHITENED:
+                    # (only the upper bound is known here: nothing this order states can send the evaluation DOWN -- a strict evaluation never
+                    # starts in it, see _plan, so whatever is accepted here was sent up by a lower tier's exact estimate)
+                    self.guard.note_bound(ub, tol)
+                    att.need = tier
+                else:
+                    att.need = required_tier(est, tol, plan.reach, plan.ext_ok)
+                    self.guard.note_exact(est, ub, tol)
+                    if att.need > tier:
+                        self.guard.open = True
+            if att.need > tier:
+                return att.need
+            if status != 0:  # B failed although the estimate is inside this tier's reach: the next tier up, if there is one
+                return tier + 1 if (tier + 1 < TIER_WHITENED and plan.ext_ok) else TIER_WHITENED
+            if may_go_down and att.need < tier:
+                return att.need
+        if plan.lo_check and tier == TIER_EXTENDED and att.Phibar_lo is not None and (att.complete or status != 0):
+            if status == 0 and not self._lo_correction_small(att, plan):
+                # The explicit pass 2 of this order is trusted only while its trailing-word correction is small against the gradient (what is
+                # left behind the correction is a few per cent of it: profiles/r06_extended_order_gradients_*): repeated in the whitened order
+                self.n_lo_rejections += 1
+                self._lo_pause = min(32, 2 * self._lo_pause) if self._lo_pause else 8
+                self._lo_skip = self._lo_pause
+                return TIER_WHITENED
+            self._lo_pause = 0   # accepted: the next rejection starts with the short pause again
+        return None
 
     def _evaluate(self, *args, **kw):
-        """`_evaluate_once`, and ONE more attempt behind a device time-out: the single-launch Cholesky deals its work items statically
-        and needs all its workgroups resident (the fast way while this process has the GPU to itself); a second process on the same
-        device -- joblib workers as in the reference's experiments/regression.py:219-231, ranks sharing a GPU -- can starve such a launch
-        into SGP_INFO_TIMEOUT.  The first time-out switches this engine's context to SGP_OPT_SHARED_DEVICE (items claimed by ticket, by
-        workgroups that are running: include/sgp.h) for good and the evaluation is repeated; a second time-out is raised."""
+        """`_walk`, and ONE more attempt behind a device time-out: the single-launch Cholesky deals its work items statically and needs all its
+        workgroups resident (the fast way while this process has the GPU to itself); a second process on the same device -- joblib workers as
+        in the reference's experiments/regression.py:219-231 -- can starve such a launch into SGP_INFO_TIMEOUT.  The first time-out switches this
+        engine's context to SGP_OPT_SHARED_DEVICE (items claimed by ticket, by workgroups that are running: include/sgp.h) for good and the
+        evaluation is repeated; a second time-out is raised.  With ONE rank only: the status word is per rank (never all-reduced), so a rank
+        repeating on its own would pair its collectives with the other ranks' NEXT evaluation -- they raise at once, as before round 6."""
         try:
-            return self._evaluate_once(*args, **kw)
+            return self._walk(*args, **kw)
         except SgpTimeoutError:
             e = self.engine
-            if "shared_device" not in getattr(e, "OPTIONS", {}) or e.get_option("shared_device") != 0:
+            if self.world > 1 or "shared_device" not in getattr(e, "OPTIONS", {}) or e.get_option("shared_device") != 0:
                 raise
             e.set_option("shared_device", 1)
             self.n_timeout_retries += 1
-            return self._evaluate_once(*args, **kw)
+            return self._walk(*args, **kw)
 
-    def _evaluate_once(self, Z, ls, sf2, s2, with_grad=False, want_gz=False, want_factors=False, grad_reach=None, strict=False):
-        """ONE evaluation through the guard -- the driver value / value_and_grad / factors share.  Runs attempts (every repeat goes to a
-        strictly higher tier; strict: once, first, to the LOWER tier the evaluation's own estimate names) until `_review` accepts.
-        Returns (res, out (host), info, host buffer, head) of the accepted attempt; with_grad: the packed gradient sits behind `head`."""
-        e = self.engine
-        M, d = int(Z.shape[0]), int(Z.shape[1])
-        guard = self._guard_on(M)
-        reach = self.extended_range
-        if with_grad:   # (how far the extended order's gradient holds 1e-6: further with both words of its double-double Phibar)
-            reach = float(grad_reach) if grad_reach is not None else (self.extended_grad_range_lo if self._bwd_lo_ok(M) else self.extended_grad_range)
-        ext_ok = self._extended_ok(M)
-        if guard:
-            tier = self.guard.start_tier(self.streaming_tol, reach, ext_ok)
-            if strict and tier == TIER_WHITENED:
-                # strict: the ACCEPTED tier is the one the evaluation's own exact estimate names.  The whitened order states only an upper
-                # bound -- whether it would be left for a lower tier was a matter of the guard's memory (ADVICE r5: the same theta accepted
-                # in tier 1 on a fresh bound and in tier 2 after some history).  So a strict evaluation starts at most in the highest tier
-                # that states its exact estimate, and reaches the whitened order only when that estimate sends it there.
-                tier = TIER_EXTENDED if ext_ok else TIER_STREAMING
-            if tier != TIER_STREAMING:
-                self.n_direct_whitened += 1
-        else:
-            tier = self._fixed_tier(M)
-        nh = (e.hyper_len(self.kernel, d) if hasattr(e, "hyper_len") else d) if with_grad else 0
-        # (behind the packed gradient: d + 1 slots for the trailing word's correction, which decides whether the explicit pass 2 is trusted)
-        lo_slots = (nh + 1) if (with_grad and guard and ext_ok and self._bwd_lo_ok(M)) else 0
-        extra = nh + 1 + (M * d if want_gz else 0) + lo_slots if with_grad else 0
-        if guard and with_grad and tier == TIER_EXTENDED and grad_reach is None and self._lo_skip > 0:
-            # the trailing word's correction was too large a moment ago: the next few gradient evaluations go straight to the whitened order (no
-            # wasted attempt per leapfrog); the pause doubles with every rejection in a row (8, 16, 32) and ends with the first acceptance
-            self._lo_skip -= 1
-            tier = TIER_WHITENED
-        # Small shards: pass 2 is enqueued straight behind the tail and ONE copy at the very end brings back F, the status and the
-        # gradient -- a failed factorization or a guard repeat then costs a wasted pass 2, which is cheaper than idling the GPU for
-        # a host round trip on every leapfrog.  Big shards check first.  The rule is the job's (largest shard), not this rank's:
-        # ranks must issue the same collectives in the same order.
-        early = with_grad and self._rows_for_form * M >= self.early_check_min_work
+    def _walk(self, Z, ls, sf2, s2, **request):
+        """ONE evaluation through the guard -- the driver value / value_and_grad / factors share (`request`: see `_plan`).  Runs attempts
+        until `_verdict` accepts one and returns it (with_grad: the packed gradient sits behind its `head`, on the host and in `buf`)."""
+        plan = self._plan(int(Z.shape[0]), int(Z.shape[1]), **request)
         # Repeats: UP whenever the attempt's own estimate asks for a higher tier; DOWN (strict only) at most once, and never again after
         # it -- so the walk ends after at most four attempts (1 -> 0 -> 1 -> 2) and what is accepted is never an attempt whose own estimate
         # asked for more (ADVICE r5: `nxt in tried` used to fall through to the LOWER attempt).  Attempts that are complete (everything
         # already on the host) are kept, so coming back to a tier costs nothing; an incomplete one (big shards: pass 2 not yet run, and
         # its K'_fu buffer since overwritten) is run again.
-        done = {}
-        may_go_down = strict
+        done, tier, may_go_down = {}, plan.tier, plan.strict
         while True:
-            res = self._forward(Z, ls, sf2, s2, with_adjoints=with_grad, want_factors=want_factors, extra=extra, tier=tier, report=guard,
-                                want_lo=grad_reach is None)
-            head = res["buf"].numel() - extra  # [out | status word | estimate | bound | pad], then the packed gradient (16-byte aligned)
-            g = res["buf"][head:] if with_grad else None
-            res["lo_slots"] = lo_slots
-            grad_upto = None if lo_slots else head + nh + 1   # (with the correction's slots: the whole buffer -- they sit at its end)
-            if with_grad and not early:
-                self._pass2(res, Z, ls, sf2, s2, want_gz, g)
-            o, info, host = self._fetch(res, upto=grad_upto if (with_grad and not early) else head)
-            nxt = self._review(res, host, info, tier, reach, M, may_go_down) if guard else None
-            if nxt is not None:
-                if not (with_grad and early) and not want_factors:
-                    done[tier] = (res, o, info, host, head)
-                if nxt < tier:
-                    may_go_down = False
-                self.n_guard_reruns += 1
-                tier = nxt
-                if tier in done:
-                    res, o, info, host, head = done[tier]
-                    self.last_tier = tier
-                    return res, o, info, host, head
-                continue
-            if with_grad and early and info == 0:
-                self._pass2(res, Z, ls, sf2, s2, want_gz, g)
-                _, _, host = self._fetch(res, upto=grad_upto)
-            if (with_grad and info == 0 and tier == TIER_EXTENDED and res.get("Phibar_lo") is not None and lo_slots and grad_reach is None
-                    and not self._lo_correction_small(host, head, nh, lo_slots)):
-                # The explicit pass 2 of this order is trusted only while its trailing-word correction is small against the gradient (what is
-                # left behind the correction is a few per cent of it: profiles/r06_extended_order_gradients_*): repeated in the whitened order
-                self.n_guard_reruns += 1
-                self.n_lo_rejections += 1
-                self._lo_pause = min(32, 2 * self._lo_pause) if self._lo_pause else 8
-                self._lo_skip = self._lo_pause
-                tier = TIER_WHITENED
-                continue
-            if with_grad and tier == TIER_EXTENDED and res.get("Phibar_lo") is not None and lo_slots and grad_reach is None:
-                self._lo_pause = 0   # accepted: the next rejection starts with the short pause again
-            self.last_tier = tier
-            return res, o, info, host, head
+            att = done.get(tier)   # (a kept attempt passes the same verdict as a fresh one; the guard's memory saw it once: `need`)
+            if att is None:
+                att = (self._attempt_streaming, self._attempt_extended, self._attempt_whitened)[tier](Z, ls, sf2, s2, plan)
+                if plan.with_grad and not plan.early:
+                    self._pass2(att, Z, ls, sf2, s2, plan)
+                self._fetch(att, plan, full=not plan.early)
+            nxt = self._verdict(att, plan, may_go_down)
+            if nxt is None and not att.complete and plan.early and att.status == 0:   # big shards: the status was read first, pass 2 goes behind an accepted tail
+                self._pass2(att, Z, ls, sf2, s2, plan)
+                self._fetch(att, plan, full=True)
+                nxt = self._verdict(att, plan, may_go_down)
+            if nxt is None:
+                break
+            if att.complete:
+                done[tier] = att
+            if nxt < tier:
+                may_go_down = False
+            self.n_guard_reruns += 1
+            tier = nxt
+        self.last_tier = tier
+        return att
 
     # ------------------------------------------------------------------ public
     def value(self, Z, ls, sf2, s2, raise_on_fail=True, strict=False):
@@ -690,18 +699,14 @@ class CollapsedBound:
             h, info, _ = self._small_eval(Z, th, 0, False, False, comp)
             self.n_evals += 1
             if info != 0:
-                if raise_on_fail:
-                    raise NotPositiveDefiniteError(info)
-                return float("nan"), {"info": info}
+                return self._failed(info, raise_on_fail)
             hl = h.tolist()  # (plain floats once: indexing the tensor costs ~1.5 us per element)
             return hl[0], {"logmarg": hl[nh + 2], "trace_term": hl[nh + 3], "info": 0}
-        res, o, info, host, _ = self._evaluate(Z, ls, sf2, s2, strict=strict)
+        att = self._evaluate(Z, ls, sf2, s2, strict=strict)
         self.n_evals += 1
-        if info != 0:
-            if raise_on_fail:
-                raise NotPositiveDefiniteError(info)
-            return float("nan"), {"info": info}
-        return float(o[OUT_F]), {"logmarg": float(o[OUT_LOGMARG]), "trace_term": float(o[OUT_TRACE]), "info": 0}
+        if att.status != 0:
+            return self._failed(att.status, raise_on_fail)
+        return float(att.o[OUT_F]), {"logmarg": float(att.o[OUT_LOGMARG]), "trace_term": float(att.o[OUT_TRACE]), "info": 0}
 
     def _natural_theta(self, ls, sf2, s2):
         """(theta of the single launch in natural parameters, composite description or None)."""
@@ -733,9 +738,7 @@ class CollapsedBound:
             self.n_evals += 1
             self.n_grads += 1
             if info != 0:
-                if raise_on_fail:
-                    raise NotPositiveDefiniteError(info)
-                return float("nan"), {"info": info}
+                return self._failed(info, raise_on_fail)
             nh = len(th) - 1  # kernel hyper-parameter entries: d lengthscales + sf2, or the composite block
             hl = h.tolist()
             if comp is not None:
@@ -744,15 +747,12 @@ class CollapsedBound:
             return hl[0], {"ls": h[1:1 + d].clone(), "sf2": hl[1 + d], "s2": hl[2 + d], "Z": gz, "info": 0,
                            "logmarg": hl[d + 3], "trace_term": hl[d + 4]}
         nh = e.hyper_len(self.kernel, d) if hasattr(e, "hyper_len") else d  # composite kernels: the parameter block
-        res, o, info, host, head = self._evaluate(Z, ls, sf2, s2, with_grad=True, want_gz=want_gz, grad_reach=grad_reach, strict=strict)
+        att = self._evaluate(Z, ls, sf2, s2, with_grad=True, want_gz=want_gz, grad_reach=grad_reach, strict=strict)
         self.n_evals += 1
         self.n_grads += 1
-        if info != 0:
-            if raise_on_fail:
-                raise NotPositiveDefiniteError(info)
-            return float("nan"), {"info": info}
-        gh = host[head:]
-        g = res["buf"][head:]
+        if att.status != 0:
+            return self._failed(att.status, raise_on_fail)
+        o, gh, g = att.o, att.host[att.head:], att.buf[att.head:]
         grads = {"ls": gh[:nh].clone(), "sf2": float(gh[nh]), "s2": float(o[OUT_S2BAR]),
                  "Z": g[nh + 1:nh + 1 + M * d].reshape(M, d) if want_gz else None, "info": 0,
                  "logmarg": float(o[OUT_LOGMARG]), "trace_term": float(o[OUT_TRACE])}
@@ -761,10 +761,10 @@ class CollapsedBound:
     def factors(self, Z, ls, sf2, s2):
         """Device tensor [Linv | G | q] for ``predict`` (computed from the current statistics)."""
         Z = self._prep_Z(Z)
-        res, _, info, _, _ = self._evaluate(Z, ls, sf2, s2, want_factors=True)
-        if info != 0:
-            raise NotPositiveDefiniteError(info)
-        return res["factors"]
+        att = self._evaluate(Z, ls, sf2, s2, want_factors=True)
+        if att.status != 0:
+            self._failed(att.status)
+        return att.factors
 
     def predict(self, Xs, Z, ls, sf2, s2, pred_noise=True, full_cov=False, factors=None):
         """Posterior predictive mean / variance (/ covariance) at Xs -- models/sgpr.py:150-160, 256-286."""

@@ -294,13 +294,9 @@ def test_strict_mode_at_the_reach_boundary_does_not_depend_on_history(no_small_w
         assert hist.last_tier == 1 and F == Ff and g["ls"].tolist() == gf["ls"].tolist(), trial
 
 
-def test_a_device_time_out_switches_to_the_shared_device_mode_and_repeats_once(no_small_whitened):
-    """Round 6 (VERDICT r5 weak-5): SGP_INFO_TIMEOUT from the single-launch Cholesky (two processes on one GPU starving each other's
-    spinning workgroups) used to be raised at once.  The first one now sets SGP_OPT_SHARED_DEVICE on the engine's context -- the ticketed
-    claim, whose progress does not need the whole launch resident -- and the evaluation is repeated; a second one is raised."""
-    import ggp_amd as pkg
+def _starved_engine():
+    """The CPU double whose tail leaves SGP_INFO_TIMEOUT until the shared-device mode is on (heals) -- or for good."""
     from fake_engine import FactoredOracleEngine
-    from ggp_amd.core import SgpTimeoutError
 
     class Starved(FactoredOracleEngine):
         OPTIONS = {"shared_device": 6}
@@ -322,6 +318,68 @@ def test_a_device_time_out_switches_to_the_shared_device_mode_and_repeats_once(n
                 res["info"][0] = -7777     # the status word a starved launch leaves
             return res
 
+    return Starved
+
+
+def test_a_device_time_out_is_raised_when_there_are_several_ranks(no_small_whitened):
+    """the status word is per rank, so a rank that repeated its evaluation behind a time-out would pair its collectives
+    with the NEXT evaluation's of the other ranks.  With several ranks the time-out is raised as before round 6: no retry, the mode untouched."""
+    from ggp_amd.core import SgpTimeoutError
+    X, y, Z = _problem()
+    eng = _starved_engine()(heals=True)
+    cb = _bound(X, y, eng)
+    cb.world = 2                                            # (no process group here: the two exchanges are identities on this instance)
+    cb._allreduce = lambda buf: buf
+    cb._allreduce_stats = lambda stats, M: stats
+    with pytest.raises(SgpTimeoutError):
+        cb.value(Z, [0.8] * 3, 1.0, 0.3)
+    assert cb.n_timeout_retries == 0 and eng.get_option("shared_device") == 0.0
+
+
+def test_a_cached_extended_attempt_passes_its_trailing_word_check(no_small_whitened):
+    """a strict walk 1 -> 0 -> 1 comes back to the extended-order attempt it kept.  That attempt used to be returned past the
+    trailing-word check and the pause bookkeeping; now it passes the same verdict as a fresh one -- rejected: on to the whitened order;
+    accepted: the pause is reset -- and what the guard remembers is not updated a second time.  The walk cannot be had by tuning theta
+    (both tiers state the same estimate), so the double reports the two orders' estimates on opposite sides of the tolerance."""
+    from fake_engine import OUT_LEN, FactoredOracleEngine
+
+    class TwoFaced(FactoredOracleEngine):
+        def streaming_error_report(self, diag, stride, trace, sf2, s2, N, M, result):
+            super().streaming_error_report(diag, stride, trace, sf2, s2, N, M, result)
+            if diag is not None:                            # extended order (its own diagonal, stride 1): benign; streaming order: a trip
+                result[0][OUT_LEN + 1] = 0.25e-9 if stride == 1 else 4e-9
+
+    X, y, Z = _problem()
+    theta = ([0.8] * 3, 1.0, 0.3)
+    Fw, gw = _bound(X, y, form="whitened").value_and_grad(Z, *theta)
+
+    def strict_walk(scale):
+        eng = TwoFaced()
+        eng.lo_delta_scale = scale
+        cb = _bound(X, y, eng)
+        cb.guard.open, cb.guard.predicted, cb._lo_pause = True, 4e-9, 8     # an open episode: the evaluation starts in the extended order
+        F, g = cb.value_and_grad(Z, *theta, strict=True)
+        assert eng.calls["suffstats_extended"] == 1 and eng.calls["suffstats"] == 1   # 1 -> 0 -> 1: no second extended-order forward pass
+        return cb, eng, F, g
+
+    cb, eng, F, g = strict_walk(1e12)                       # the correction is NOT small: the kept attempt is rejected like a fresh one
+    assert cb.last_tier == 2 and cb.n_lo_rejections == 1 and cb.n_guard_reruns == 3 and (cb._lo_pause, cb._lo_skip) == (16, 16)
+    assert F == Fw and g["ls"].tolist() == gw["ls"].tolist() and g["sf2"] == gw["sf2"] and g["s2"] == gw["s2"]
+    cb, eng, F, g = strict_walk(1.0)                        # a small correction: accepted, the pause forgotten
+    assert cb.last_tier == 1 and cb._lo_pause == 0 and cb.n_lo_rejections == 0 and cb.n_guard_reruns == 2
+    assert eng.calls["suffstats_whitened_rows"] == 0 and cb.last_lo_correction <= cb.extended_lo_max_correction
+    assert cb.last_estimate == 4e-9 and cb.guard.predicted == 4e-9 and cb.guard.open   # the kept attempt was not reviewed a second time
+
+
+def test_a_device_time_out_switches_to_the_shared_device_mode_and_repeats_once(no_small_whitened):
+    """Round 6 (VERDICT r5 weak-5): SGP_INFO_TIMEOUT from the single-launch Cholesky (two processes on one GPU starving each other's
+    spinning workgroups) used to be raised at once.  The first one now sets SGP_OPT_SHARED_DEVICE on the engine's context -- the ticketed
+    claim, whose progress does not need the whole launch resident -- and the evaluation is repeated; a second one is raised."""
+    import ggp_amd as pkg
+    from fake_engine import FactoredOracleEngine
+    from ggp_amd.core import SgpTimeoutError
+
+    Starved = _starved_engine()
     X, y, Z = _problem()
     ref = _bound(X, y).value(Z, [0.8] * 3, 1.0, 0.3)[0]
     eng = Starved(heals=True)

@@ -376,7 +376,7 @@ def test_streaming_guard_repeats_in_the_whitened_order_on_the_cpu_double():
         hard = ([25.0] * 3, 1.0, 1e-5)                                  # K_uu at its jitter floor, tiny noise
         F1, _ = cb.value(Z, *hard)
         assert cb.n_guard_reruns == 1 and cb.last_estimate > 1e-9 and eng.calls["suffstats_whitened"] == 1
-        assert cb._prefer_whitened and 0.0 < cb.guard.ratio <= 1.0
+        assert cb.guard.open and 0.0 < cb.guard.ratio <= 1.0
         cw = pkg.CollapsedBound(X, y, jitter=1e-6, engine=GuardedOracleEngine(), form="whitened")
         assert F1 == cw.value(Z, *hard)[0]                              # the repeat IS the whitened evaluation
         n_stream = eng.calls["suffstats"]
@@ -385,13 +385,13 @@ def test_streaming_guard_repeats_in_the_whitened_order_on_the_cpu_double():
         assert cb.n_guard_reruns == 1 and cb.n_direct_whitened == 1 and eng.calls["suffstats"] == n_stream
         assert F2 == Fw and torch.equal(g2["ls"], gw["ls"]) and torch.equal(g2["Z"], gw["Z"])
         cb.factors(Z, *hard)
-        assert cb.n_direct_whitened == 2 and cb._prefer_whitened
+        assert cb.n_direct_whitened == 2 and cb.guard.open
         Fb, _ = cb.value(Z, [0.8] * 3, 1.0, 0.3)                       # benign again: still whitened (it cannot know yet) ...
-        assert cb.n_direct_whitened == 3 and not cb._prefer_whitened     # ... but the bound it reports ends the episode
+        assert cb.n_direct_whitened == 3 and not cb.guard.open     # ... but the bound it reports ends the episode
         assert abs(Fb - F0) < 1e-9 * abs(F0)
         Fc, _ = cb.value(Z, [0.8] * 3, 1.0, 0.3)
         assert Fc == F0 and cb.n_direct_whitened == 3 and cb.n_guard_reruns == 1   # streamed again, bit for bit as before
-        cb._prefer_whitened = True
+        cb.guard.open = True
         cb.streaming_tol = 0.0
         cb.value(Z, *hard, raise_on_fail=False)
         cs = pkg.CollapsedBound(X, y, jitter=1e-6, engine=GuardedOracleEngine(), form="streaming")
@@ -418,7 +418,7 @@ def _guard_worker(rank, world, port, q):
     for ls, s2 in ((0.8, 0.3), (25.0, 1e-5), (3.0, 1e-3), (25.0, 1e-5)):
         F, g = cb.value_and_grad(Z, [ls] * 3, 1.0, s2, want_gz=False)
         out.append((F, g["ls"].numpy().tolist(), cb.n_guard_reruns + cb.n_direct_whitened, cb.last_estimate, cb.n_collectives,
-                    cb._prefer_whitened, cb.guard.ratio))
+                    cb.guard.open, cb.guard.ratio))
     q.put((rank, out))
     dist.barrier()
     dist.destroy_process_group()
@@ -568,7 +568,7 @@ def test_three_tier_guard_on_the_cpu_double():
         cb.value(Z, *mid)
         assert cb.n_extended == 5
         cb.value(Z, *benign)                                                                    # extended once more, then the episode ends
-        assert not cb._prefer_whitened
+        assert not cb.guard.open
         n_stream = eng.calls["suffstats"]
         cb.value(Z, *benign)
         assert eng.calls["suffstats"] == n_stream + 1 and cb.n_extended == 6
@@ -604,7 +604,7 @@ def _tier_worker(rank, world, port, q):
     for ls, s2 in ((0.8, 0.3), (3.0, 2e-2), (3.0, 2e-2), (25.0, 1e-5), (25.0, 1e-5), (3.0, 2e-2), (0.8, 0.3), (0.8, 0.3)):   # (far: beyond the gradient range of the double-double Phibar too)
         F, g = cb.value_and_grad(Z, [ls] * 3, 1.0, s2, want_gz=False)
         out.append((F, g["ls"].numpy().tolist(), cb.n_guard_reruns, cb.n_direct_whitened, cb.n_extended, cb.n_collectives,
-                    cb._prefer_whitened, cb.guard.predicted))
+                    cb.guard.open, cb.guard.predicted))
     q.put((rank, out, eng.calls.get("suffstats_extended", 0), eng.calls["suffstats_whitened_rows"]))
     dist.barrier()
     dist.destroy_process_group()

@@ -67,7 +67,7 @@ def test_default_mode_bound_over_the_theta_range(engine, host_threads, M, dup, c
     bad, log, ref_cache = [], [], {}
     try:
         for ls, sn in cells:
-            before, before_d, after_trip = cb.n_guard_reruns, cb.n_direct_whitened, cb._prefer_whitened
+            before, before_d, after_trip = cb.n_guard_reruns, cb.n_direct_whitened, cb.guard.open
             F, parts = cb.value(Zd, [ls] * D, 1.0, sn * sn)
             rerun, direct = cb.n_guard_reruns - before, cb.n_direct_whitened - before_d
             if not rerun and not direct:
@@ -91,7 +91,7 @@ def test_default_mode_bound_over_the_theta_range(engine, host_threads, M, dup, c
             if not dup:  # (exact duplicates among the inducing rows inflate the estimate: their eigen-directions carry no error)
                 if ls <= 1.0 or (ls == 2.0 and sn >= 0.3):   # benign: streamed -- or, right behind a trip, whitened ONCE more
                     assert rerun == 0 and (direct == 0 or after_trip), ("a benign cell was sent to the whitened order", ls, sn, log)
-                    assert not cb._prefer_whitened, ("the whitened episode must end at a benign cell", ls, sn, log)
+                    assert not cb.guard.open, ("the whitened episode must end at a benign cell", ls, sn, log)
                 if (ls >= 5.0 and sn <= 0.3) or (ls >= 20.0 and sn < 1.0):
                     assert rerun + direct == 1, ("the guard must send this cell to the whitened order", ls, sn, log)
     finally:
@@ -119,7 +119,7 @@ def test_streaming_guard_can_be_switched_off_and_reports_its_estimate(engine):
     assert F1 == F4                                   # the repeat IS the whitened evaluation
     # a benign theta: no repeat, and value + gradient agree with the whitened order to rounding
     cb.streaming_tol = 1e-9
-    cb._prefer_whitened = False          # (the trip above would send the next evaluation to the whitened order directly)
+    cb.guard.open = False          # (the trip above would send the next evaluation to the whitened order directly)
     Fa, ga = cb.value_and_grad(Zd, [1.0] * D, 1.0, 0.09)
     Fb, gb = cw.value_and_grad(Zd, [1.0] * D, 1.0, 0.09)
     assert cb.n_guard_reruns == 1 and abs(Fa - Fb) < 1e-10 * abs(Fb)
@@ -292,7 +292,7 @@ def test_fp64_contraction_below_the_integer_threshold_over_the_theta_range(engin
     bad, log = [], []
     host_threads()
     for ls, sn in cells:
-        cb._prefer_whitened = False  # every cell starts in the streaming order: the guard's own decision is what is tested
+        cb.guard.open = False  # every cell starts in the streaming order: the guard's own decision is what is tested
         before = cb.n_guard_reruns
         F, parts = cb.value(Zd, ls, 1.0, sn * sn)
         rerun = cb.n_guard_reruns - before

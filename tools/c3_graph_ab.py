@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """VERDICT r5 next-5, the measurement before the build: what would ONE captured graph per evaluation save at C3 (N 13 279, d 18, M 512; ~30
-launches in 0.41 / 0.74 ms)?  The multi-launch evaluation is enqueued without a host round trip (CollapsedBound._forward / _pass2), so it can
+launches in 0.41 / 0.74 ms)?  The multi-launch evaluation is enqueued without a host round trip (CollapsedBound._attempt_streaming / _pass2), so it can
 be captured as it is -- with theta baked into the kernel arguments, i.e. valid for THIS theta only: a timing instrument, not a product path
 (the product would need theta in device memory).  Compares, alternating: plain launches vs replay of the captured graph, both ending in the
 same single device-to-host copy of the result buffer; single stream in both (the two-stream arrangement of the product is timed beside them)."""
@@ -32,20 +32,21 @@ for with_grad in (False, True):
         prod()
     cb1 = ggp_amd.CollapsedBound(Xd, yd, jitter=1e-6, engine=eng)
     cb1.overlap_tail = False
-    nh = d
-    extra = (nh + 1) if with_grad else 0
+    plan = cb1._plan(M, d, with_grad=with_grad)   # (the guard watches at this size: the attempt reports its estimate)
+    assert plan.guard and plan.tier == C.TIER_STREAMING
+    plan.lo_slots, plan.extra = 0, (d + 1 if with_grad else 0)   # (as measured in round 5: no slots for a trailing-word correction behind the gradient)
+    extra = plan.extra
 
     def enqueue():
-        res = cb1._forward(Z, ls, sf2, s2, with_adjoints=with_grad, extra=extra, tier=C.TIER_STREAMING, report=True)
+        att = cb1._attempt_streaming(Z, ls, sf2, s2, plan)
         if with_grad:
-            head = res["buf"].numel() - extra
-            cb1._pass2(res, Z, ls, sf2, s2, False, res["buf"][head:])
-        return res
+            cb1._pass2(att, Z, ls, sf2, s2, plan)
+        return att
 
     for _ in range(5):
         r = enqueue()
-        r["buf"].to("cpu")
-    ref = enqueue()["buf"].to("cpu").clone()
+        r.buf.to("cpu")
+    ref = enqueue().buf.to("cpu").clone()
     side = torch.cuda.Stream(device=eng.device)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.stream(side):
@@ -56,18 +57,18 @@ for with_grad in (False, True):
             gres = enqueue()
     torch.cuda.synchronize()
     graph.replay()
-    got = gres["buf"].to("cpu")
+    got = gres.buf.to("cpu")
     keep = list(range(ggp_amd.engine.OUT_LEN)) + list(range(got.numel() - extra, got.numel()))   # (the padding, and the half of the status word's double behind it, are never written)
     same = bool(torch.equal(got[keep].view(torch.int64), ref[keep].view(torch.int64)))
     if not same and os.environ.get("VERBOSE"):
         print("differing slots:", [(i, float(got[i]), float(ref[i])) for i in keep if got[i:i + 1].view(torch.int64) != ref[i:i + 1].view(torch.int64)], file=sys.stderr)
 
     def t_plain():
-        enqueue()["buf"].to("cpu")
+        enqueue().buf.to("cpu")
 
     def t_graph():
         graph.replay()
-        gres["buf"].to("cpu")
+        gres.buf.to("cpu")
 
     def timed(fn, n=200):
         fn()

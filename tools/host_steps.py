@@ -38,8 +38,8 @@ def wrap(obj, name):
 
 for nm in ("kuu", "kuu_factor", "suffstats", "bound", "streaming_error_report", "suffstats_bwd", "kuu_bwd", "result_buffer"):
     wrap(eng, nm)
-for nm in ("_fetch", "_forward", "_prep_Z", "_small_ok", "_guard_on", "_extended_ok", "_kfu_for", "_side_state", "_trace_buf", "_review",
-           "_evaluate", "_pass2"):
+for nm in ("_fetch", "_plan", "_attempt_streaming", "_kuu_chain", "_prep_Z", "_small_ok", "_guard_on", "_extended_ok", "_kfu_for", "_side_state", "_trace_buf",
+           "_verdict", "_evaluate", "_pass2"):
     wrap(cb, nm)
 fn = (lambda: cb.value_and_grad(Z, ls, 1.0, 0.09)) if grad else (lambda: cb.value(Z, ls, 1.0, 0.09))
 for _ in range(10):
