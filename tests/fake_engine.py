@@ -196,6 +196,49 @@ class OracleEngine:
                 cov = cov + s2 * torch.eye(Xs.shape[0], dtype=torch.float64)
         return mean, var, cov
 
+    def mixture_predict(self, X, y, Xs, Z, ls, sf2, s2, jitter=1e-6, kernel="rbf", pred_noise=True, full_cov=False, gate_jitter=None):
+        """HipEngine.mixture_predict in float64, sample by sample in the whitened order with the explicit inverses (A = L^-1 K_uf,
+        B = I + A A^T / s2, L_B^-1); ``Z``: M x d, or S x M x d for inducing inputs of their own per sample."""
+        self.calls["mixture_predict"] = self.calls.get("mixture_predict", 0) + 1
+        S, T, d, kid = len(ls), Xs.shape[0], X.shape[1], KID[kernel]
+        if Z.dim() == 3 and (Z.shape[0] != S or Z.shape[2] != d):
+            raise ValueError("a per-sample Z must be S x M x d")
+        if any(len(row) != d for row in ls) or len(sf2) != S or len(s2) != S:
+            raise ValueError("ls must be S x d, sf2 and s2 of length S")
+        want_gate = full_cov and gate_jitter is not None
+        mean, var = torch.empty(S, T, dtype=torch.float64), torch.empty(S, T, dtype=torch.float64)
+        cov = torch.empty(S, T, T, dtype=torch.float64) if full_cov else None
+        info = torch.zeros(S, dtype=torch.int32)
+        gate = torch.zeros(S, dtype=torch.int32) if want_gate else None
+        for k in range(S):
+            Zk, lst, f2, n2 = (Z[k] if Z.dim() == 3 else Z), self._ls(ls[k], d), float(sf2[k]), float(s2[k])
+            M = Zk.shape[0]
+            I = torch.eye(M, dtype=torch.float64)
+            L, bad = torch.linalg.cholesky_ex(O.kuu(Zk, lst, f2, float(jitter), kid))
+            if int(bad) == 0:
+                Linv = torch.linalg.solve_triangular(L, I, upper=False)
+                A = Linv @ O.kernel_from_r2(O.sqdist(Zk, X, lst), f2, kid)
+                LB, bad = torch.linalg.cholesky_ex(I + A @ A.T / n2)
+                bad = int(bad) + (M if int(bad) else 0)
+            if int(bad) != 0:
+                info[k] = int(bad)
+                mean[k], var[k] = float("nan"), float("nan")
+                if full_cov:
+                    cov[k] = float("nan")
+                continue
+            LBinv = torch.linalg.solve_triangular(LB, I, upper=False)
+            q = LBinv @ (A @ y)
+            As = Linv @ O.kernel_from_r2(O.sqdist(Zk, Xs, lst), f2, kid)
+            C = LBinv @ As
+            noise = n2 if pred_noise else 0.0
+            mean[k] = C.T @ q / n2
+            var[k] = f2 - (As * As).sum(0) + (C * C).sum(0) + noise
+            if full_cov:
+                cov[k] = O.kernel_from_r2(O.sqdist(Xs, Xs, lst), f2, kid) - As.T @ As + C.T @ C + noise * torch.eye(T, dtype=torch.float64)
+                if want_gate:
+                    gate[k] = int(torch.linalg.cholesky_ex(cov[k] + float(gate_jitter) * torch.eye(T, dtype=torch.float64))[1])
+        return {"mean": mean, "var": var, "cov": cov, "info": info, "gate": gate}
+
     # ---- SVGP (oracle.svgp_oracle) ----
     def svgp_elbo(self, Xb, yb, Z, ls, sf2, s2, m, LS, N_total, jitter=1e-6, kernel="rbf", likelihood="gaussian",
                   with_grads=False):

@@ -1237,7 +1237,9 @@ def test_mixture_predictive_edge_shapes(engine, N, M, T, d, S):
     Xt = torch.randn(T, d, dtype=torch.float64, generator=g)
     Z = (X[torch.randperm(N, generator=g)[:M]] if M <= N else torch.randn(M, d, dtype=torch.float64, generator=g)).clone()
     # lengthscales below the inducing-point spacing (129 points in 2-D sit closer than 70 in 3-D): a test of the tiling, not of
-    # cond(K_uu) eps -- at ls 0.5-0.8 the d = 2 case differs from the (streaming-order) oracle by 5e-7 everywhere
+    # cond(K_uu) eps -- at ls 0.5-0.8 the d = 2 case differs from the (streaming-order) oracle by 5e-7 everywhere.  That difference is
+    # the oracle's: against long double the kernels stay within a few 1e-11 of the condition scale at such a cell (300-65-2-rbf of
+    # tests/test_stream_predict_gpu.py), where the streaming-order float64 evaluation is 1e-9 of it away
     ls = (0.5 + 0.3 * torch.rand(S, d, dtype=torch.float64, generator=g)) * (0.4 if d <= 2 else 1.0)
     sf2 = 0.8 + 0.5 * torch.rand(S, dtype=torch.float64, generator=g)
     s2 = 0.05 + 0.1 * torch.rand(S, dtype=torch.float64, generator=g)
